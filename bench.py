@@ -1,8 +1,28 @@
 """Throughput of the SALP env-step hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline figure needs and no more: it creates the
+envs, runs W untimed and K timed launches, writes the last launch's outputs if
+`--dump-outputs DIR` is given and prints the result line.  `--full` adds every
+other leg after the timed region (each with its `--no-...` switch): the
+divergence counts, the sampled oracle replay (`parity_sampled`), the lock-step /
+given-action / chained-32 / per-env step paths, the steady-state rate, the
+committed PMC summaries beside the rooflines, the config-5 PPO leg and the CPU
+baseline.
+
+`--dump-outputs DIR` (rank 0): what the timed path left after its last launch,
+for a fixed seeded sample of env ids (all of them up to DUMP_ENVS), as float32 /
+float64 `DIR/<name>.npy`: the rollout-buffer tensors obs, obs_before, actions,
+rewards, dones [capacity, k, ...], steps_done [k], the env state [fields, k] and
+env_ids [k].  The files hold finite numbers only: a diverged env carries NaN
+(as the reference's integrator does), so each floating tensor is written with
+its non-finite elements set to 0 and a `<name>_nonfinite.npy` beside it (0
+finite, 1 NaN, 2 +inf, 3 -inf).  Equal arguments give equal inputs (Philox
+keyed by --seed and the global env id), so two builds can be compared array
+for array.
 
 `--gpus N` (N > 1) without torchrun's environment starts N ranks itself: it
 runs `torch.distributed.run` as a child process before anything touches the
@@ -66,6 +86,42 @@ HOT_FIELDS = slice(FIELD["v0"], FIELD["ang2"] + 1)   # kinematic state: NaN once
 
 
 STEADY_WARM, STEADY_TIMED = 40, 20
+# --dump-outputs: at most this many envs (a seeded sample of a larger batch) and this many bytes in all
+DUMP_ENVS, DUMP_SEED, DUMP_MAX_BYTES = 8192, 20250, 56 << 20
+DUMP_NAN, DUMP_POS_INF, DUMP_NEG_INF = 1.0, 2.0, 3.0   # <name>_nonfinite.npy codes (0 = finite)
+
+
+def dump_outputs(path, env, bufs, done):
+    """Write what the timed path left after its last launch (the rollout-buffer
+    tensors, steps_done and the env state) for a fixed sample of env ids as
+    float32 / float64 .npy files under `path`.  Every file holds finite numbers
+    only: an env whose integration diverged carries NaN (as the reference's
+    does), so each floating tensor <name> is written with its non-finite
+    elements set to 0 beside <name>_nonfinite (float32: 0 finite, 1 NaN,
+    2 +inf, 3 -inf), which says where they were."""
+    import numpy as np
+    n = env.n_envs
+    state = env.get_state()
+    per_env = sum(v[:, :1].numel() * 8 for v in bufs.values()) + state.shape[0] * 12 + 16
+    k = max(1, min(n, DUMP_ENVS, DUMP_MAX_BYTES // per_env))
+    ids = np.arange(n) if k == n else np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False))
+    sel = torch.as_tensor(ids, dtype=torch.int64, device=state.device)
+    os.makedirs(path, exist_ok=True)
+    out = {"steps_done": done.index_select(0, sel).to(torch.float64),
+           "env_ids": (sel + env.env_id_offset).to(torch.float64)}
+    for name, t in [*bufs.items(), ("state", state)]:
+        t = t.index_select(1, sel)
+        if not t.is_floating_point():
+            out[name] = t.to(torch.float32)
+            continue
+        code = torch.zeros(t.shape, dtype=torch.float32, device=t.device)
+        code[torch.isnan(t)] = DUMP_NAN
+        code[t == float("inf")] = DUMP_POS_INF
+        code[t == float("-inf")] = DUMP_NEG_INF
+        out[name] = torch.where(code == 0, t, torch.zeros_like(t))
+        out[name + "_nonfinite"] = code
+    for name, t in out.items():
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
 
 
 def summary_order(path):
@@ -120,12 +176,18 @@ def parse(argv=None):
     ap.add_argument("--chunk", type=int, default=64,
                     help="ticks between env-step boundaries (64 with q = 560: profiles/r5_experiments.md r5j-r5k)")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="rank 0 writes the last timed launch's outputs as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run every other leg: divergence counts, oracle replay, "
+                         "the step paths, steady state, PMC summaries, the PPO leg, the CPU baseline")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-lockstep", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-lockstep", action="store_true",
+                    help="--full without the step paths and the steady-state rate")
     ap.add_argument("--no-parity-check", action="store_true",
-                    help="skip the sampled oracle replay after the timed region")
-    ap.add_argument("--no-ppo", action="store_true", help="skip the config-5 PPO leg")
+                    help="--full without the sampled oracle replay after the timed region")
+    ap.add_argument("--no-ppo", action="store_true", help="--full without the config-5 PPO leg")
     ap.add_argument("--ppo-envs", type=int, default=32768, help="PPO leg: envs per GPU (BASELINE configs[4])")
     ap.add_argument("--ppo-steps", type=int, default=256, help="PPO leg: n_steps per collection")
     ap.add_argument("--dry-run", action="store_true",
@@ -412,6 +474,13 @@ def main(argv=None):
     a = parse(argv)
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    # the legs beside the headline run only with --full, each unless switched off
+    do_parity = a.full and not a.no_parity_check
+    do_paths = a.full and not a.no_lockstep
+    do_ppo = a.full and not a.no_ppo
+    do_cpu = a.full and not a.no_cpu_baseline
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(a, argv))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -465,8 +534,10 @@ def main(argv=None):
     barrier()
     torch.cuda.synchronize()
     s0 = int(done.sum())
-    done0 = done.clone()
-    finite0 = torch.isfinite(env.get_state()[HOT_FIELDS]).all(0)
+    if a.full:
+        done0 = done.clone()
+        finite0 = torch.isfinite(env.get_state()[HOT_FIELDS]).all(0)
+        torch.cuda.synchronize()
     # HIP events on the stream the kernel is launched on (torch's current stream)
     stream = torch.cuda.current_stream(dev)
     starts = [torch.cuda.Event(enable_timing=True) for _ in range(a.steps)]
@@ -483,25 +554,29 @@ def main(argv=None):
     steps_local = int(done.sum()) - s0
     kern_ms = sum(s.elapsed_time(e) for s, e in zip(starts, ends)) / a.steps
 
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, env, bufs, done)
+
     # SURVEY.md §5 failure detection: envs whose explicit integration diverged
     # (the reference's own blow-up, test_reference_blowup_is_reproduced) at
     # the end of the run, and the non-finite observations among the last
     # `cap` env-steps of every env held in the rollout buffer.
-    st = env.get_state()
-    finite1 = torch.isfinite(st[HOT_FIELDS]).all(0)
-    diverged = int((~finite1).sum())
-    bad_rows = int((~torch.isfinite(bufs["obs"]).all(-1)).sum())
-    # env-steps of the envs whose kinematic state was finite at both ends of
-    # the timed region (an env that diverges stays NaN until its 500-cycle
-    # timeout, longer than the timed region)
-    finite_steps = int(((done - done0) * (finite0 & finite1)).sum())
+    if a.full:
+        st = env.get_state()
+        finite1 = torch.isfinite(st[HOT_FIELDS]).all(0)
+        diverged = int((~finite1).sum())
+        bad_rows = int((~torch.isfinite(bufs["obs"]).all(-1)).sum())
+        # env-steps of the envs whose kinematic state was finite at both ends of
+        # the timed region (an env that diverges stays NaN until its 500-cycle
+        # timeout, longer than the timed region)
+        finite_steps = int(((done - done0) * (finite0 & finite1)).sum())
 
     # Parity at the bench's own horizon (the checker, after the timed region):
     # sampled env ids replayed from creation on the C oracle for exactly the
     # env-steps each completed plus its in-flight cycle; state and the last
     # `cap` buffer rows compared bit for bit (oracle/sampled.py).
     parity = None
-    if rank == 0 and not a.no_parity_check:
+    if rank == 0 and do_parity:
         from oracle import sampled
         t_chk = time.perf_counter()
         parity = sampled.check(st.cpu().numpy(), done.cpu().numpy(), {k: v.cpu().numpy() for k, v in bufs.items()},
@@ -519,7 +594,7 @@ def main(argv=None):
     # * chained k-step: salp_step_random(32), every env runs its 32 env-steps back
     #   to back on k_rollout (max_steps) and stops (from 32 env-steps per call on).
     lock = given = chained32 = gym_rate = None
-    if not a.no_lockstep:
+    if do_paths:
         env.step_random(1)
         torch.cuda.synchronize()
 
@@ -547,7 +622,7 @@ def main(argv=None):
     # the full sin / cos path.  A fresh handle of the same
     # size runs STEADY_WARM untimed launches, then STEADY_TIMED timed ones.
     steady = None
-    if not a.no_lockstep and world == 1:
+    if do_paths and world == 1:
         senv = BatchedSalpEnv(n, params=default_params(), seed=a.seed + 7, device=dev.index)
         sdone = torch.zeros(n, dtype=torch.int64, device=dev)
         for _ in range(STEADY_WARM):
@@ -563,7 +638,7 @@ def main(argv=None):
         del senv
 
     ppo = None
-    if not a.no_ppo:
+    if do_ppo:
         del bufs
         torch.cuda.empty_cache()
         ppo = ppo_leg(a, rank, world, dev)
@@ -571,16 +646,19 @@ def main(argv=None):
     elapsed, steps_total, kern_ms, lock_total = reduce_run(elapsed, steps_local, kern_ms, lock, device=dev)
     given_total = reduce_sums([given or 0.0], device=dev)[0] if given is not None else None
     chained32_total = reduce_sums([chained32 or 0.0], device=dev)[0] if chained32 is not None else None
-    diverged_total, bad_rows_total, finite_total = reduce_sums([diverged, bad_rows, finite_steps], device=dev)
+    if a.full:
+        diverged_total, bad_rows_total, finite_total = reduce_sums([diverged, bad_rows, finite_steps], device=dev)
     seen_world = dist.get_world_size() if world > 1 else 1
     if rank != 0:
         dist.destroy_process_group()
         return
 
-    prof = pmc_profile(n, a.tick_budget, a.chunk)
-    from grasp_lab_salp_amd import _codeobj
-    from grasp_lab_salp_amd._lib import LIB_PATH
-    kernel_sha = _codeobj.kernel_sha(LIB_PATH, _codeobj.ROLLOUT_KERNEL)
+    prof, kernel_sha = (None, None, "PMC summaries are matched to the library's kernel with --full"), None
+    if a.full:
+        prof = pmc_profile(n, a.tick_budget, a.chunk)
+        from grasp_lab_salp_amd import _codeobj
+        from grasp_lab_salp_amd._lib import LIB_PATH
+        kernel_sha = _codeobj.kernel_sha(LIB_PATH, _codeobj.ROLLOUT_KERNEL)
     budget_ticks = float(-(-a.tick_budget // a.chunk) * a.chunk) * n * a.steps * world
     steps_per_launch = steps_local / a.steps
     bytes_launch = steps_per_launch * BYTES_PER_ENV_STEP
@@ -602,6 +680,7 @@ def main(argv=None):
         "world_size": seen_world,
         "steps": a.steps,
         "warmup": a.warmup,
+        "full": a.full,
         "ms_per_step": elapsed / a.steps * 1e3,
         "higher_is_better": True,
         "scaling": "weak",
@@ -612,9 +691,6 @@ def main(argv=None):
                                "canonical make_env robot (src/train_robot.py:11-21), 2 obstacles",
                    "n_envs_per_gpu": n, "tick_budget": a.tick_budget, "chunk": a.chunk, "rollout_capacity": cap,
                    "parallelism": f"env-shard x{world}"},
-        "finite_env_steps_per_sec": finite_total / elapsed,
-        "finite_note": "env-steps of envs whose kinematic state was finite at the start and at the end of the timed "
-                       "region (diverged envs carry NaN, as the reference's integrator does, and count in value)",
         "ticks_per_env_step": tps,
         "ticks_per_env_step_source": tps_src,
         "ticks_per_sec": steps_total * tps / elapsed,
@@ -648,11 +724,16 @@ def main(argv=None):
                            "on k_rollout with max_steps (each env 32 env-steps back to back); per-env gym: the unchanged "
                            "drop-in SalpRobotEnv.step (one env, src/train_robot.py:11-21's robot) on the host clock, "
                            "200 env-steps of U(action box) actions, rank 0 of a 1-GPU run (k_step_wave)",
-        "divergence": {"diverged_envs_at_end": diverged_total, "envs": n * world,
-                       "nonfinite_obs_rows_in_buffer": bad_rows_total, "buffer_rows": cap * n * world,
-                       "note": "the reference integrator itself diverges for some actions (jet_time < dt); "
-                               "such envs carry NaN until the 500-cycle timeout resets them"},
     }
+    if a.full:
+        res["finite_env_steps_per_sec"] = finite_total / elapsed
+        res["finite_note"] = ("env-steps of envs whose kinematic state was finite at the start and at the end of the "
+                              "timed region (diverged envs carry NaN, as the reference's integrator does, and count "
+                              "in value)")
+        res["divergence"] = {"diverged_envs_at_end": diverged_total, "envs": n * world,
+                             "nonfinite_obs_rows_in_buffer": bad_rows_total, "buffer_rows": cap * n * world,
+                             "note": "the reference integrator itself diverges for some actions (jet_time < dt); "
+                                     "such envs carry NaN until the 500-cycle timeout resets them"}
     # fp64 VALU roofline: algorithmic flops (F_TICK_ALGO per executed env-tick)
     # and, where a PMC summary of this configuration exists, executed flops
     fl_algo = F_TICK_ALGO * env_ticks_per_launch / (kern_ms / 1e3) / 1e12
@@ -682,7 +763,7 @@ def main(argv=None):
         res["parity_sampled"] = parity
     if ppo is not None:
         res["ppo"] = ppo
-    if not a.no_cpu_baseline:
+    if do_cpu:
         # rank 0, after every rank's timed region (the other ranks have left):
         # the same bounded oracle sample at every N, on rank 0's CPU share
         res["cpu_baseline"] = cpu_baseline(a.cpu_baseline_seconds)

@@ -46,6 +46,17 @@ def test_gpus_1_runs_in_process():
     assert res["n_gpus"] == 1 and res["world_size"] == 1 and res["env_id_offsets"] == [0]
 
 
+def test_extra_legs_and_output_dump_are_opt_in():
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = bench.parse(["--full", "--dump-outputs", "some/dir"])
+    assert a.full is True and a.dump_outputs == "some/dir"
+    r = _run(["--gpus", "1", "--steps", "0"])
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
 def test_world_size_mismatch_is_an_error():
     r = _run(["--gpus", "2", "--dry-run"], env_extra={"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
     assert r.returncode != 0

@@ -8,7 +8,7 @@ OUT=${OUT:-gpurun_out/collect_cq_ab.txt}
 for r in $(seq ${ROUNDS:-2}); do
     for cq in ${CQS:-176:340 192:400}; do
         c=${cq%%:*}; q=${cq##*:}
-        p=$(SALP_COLLECT_CHUNK=$c SALP_PAIR_COLLECT_Q8=$q timeout -k 10 300 python bench.py --steps 2 --warmup 1 \
+        p=$(SALP_COLLECT_CHUNK=$c SALP_PAIR_COLLECT_Q8=$q timeout -k 10 300 python bench.py --full --steps 2 --warmup 1 \
             --no-cpu-baseline --no-lockstep --no-parity-check 2>/dev/null | grep '^{' | python -c "
 import json, sys
 d = json.load(sys.stdin)['ppo']

@@ -9,7 +9,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 1
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 TAG=${TAG:-r5c}
-ARGS="--steps 1 --warmup 0 --no-cpu-baseline --no-lockstep --no-parity-check"
+ARGS="--full --steps 1 --warmup 0 --no-cpu-baseline --no-lockstep --no-parity-check"
 # PROBE=1: profile tools/collect_pmc_probe.py (salp_collect alone) instead of the bench
 CMD="bench.py $ARGS"
 [ "${PROBE:-0}" = 1 ] && CMD="tools/collect_pmc_probe.py"

@@ -8,7 +8,7 @@ OUT=${OUT:-gpurun_out/ppo_ab.txt}
 for r in $(seq ${ROUNDS:-2}); do
     for lib in ${LIBS:-product}; do
         l=$lib; [ "$lib" = product ] && l=""
-        v=$(SALP_AB_OLD_ABI=1 SALP_LIB=$l timeout -k 10 400 python bench.py --steps 2 --warmup 1 --no-cpu-baseline \
+        v=$(SALP_AB_OLD_ABI=1 SALP_LIB=$l timeout -k 10 400 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline \
             --no-lockstep --no-parity-check 2>/dev/null | grep '^{' | python -c "
 import json, sys
 d = json.load(sys.stdin)['ppo']

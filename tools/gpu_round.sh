@@ -20,8 +20,8 @@ if [ -z "$SKIP_TESTS" ]; then
     step pytest_gpu 600 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread ${PYTEST_ARGS}
     step smoke 300 python -u -c "import __graft_entry__ as g; g.smoke()"
 fi
-step bench 400 python -u bench.py ${BENCH_ARGS}
+step bench 400 python -u bench.py --full ${BENCH_ARGS}
 if [ -z "$SKIP_PROF" ]; then
     step prof 400 rocprofv3 --kernel-trace --stats --output-format csv -d "gpurun_out/${TAG}_prof" -o run \
-        -- python3 bench.py --no-cpu-baseline ${PROF_ARGS:---no-lockstep}
+        -- python3 bench.py --full --no-cpu-baseline ${PROF_ARGS:---no-lockstep}
 fi

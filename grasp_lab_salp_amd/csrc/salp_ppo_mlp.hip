@@ -30,9 +30,11 @@
 // flat gradient (one RCCL message).  The hidden units' tanh is the collection's
 // (salp_tanh.h: branch-free, ~1e-7 from torch's; the library's tanhf was 35
 // VALU instructions of the row kernel's ~115 per unit, profiles/r6c_pmc_update_summary.json).  Row math is float32 like torch's; reductions are fp64;
-// the results agree with torch to float32 rounding (tests/test_gpu_ppo_mlp.py),
-// not bit for bit (different summation orders), and are deterministic (no
-// floating-point atomics: k_mlp_adam's one atomic counts arriving blocks).
+// the results agree with torch to float32 rounding (tests/test_gpu_ppo_mlp.py;
+// tests/test_gpu_ppo_mlp_ref.py holds the multi-tile path, every obs_dim and
+// Adam to float64 references), not bit for bit (different summation orders),
+// and are deterministic (no floating-point atomics: k_mlp_adam's one atomic
+// counts arriving blocks).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -622,7 +624,8 @@ constexpr int NT_APPLY = 1024;
 constexpr int AP_MAX = 11;   // parameters per thread
 static_assert((int64_t)NT_APPLY * AP_MAX >= 2 * (H * DP + H + H * H + H) + NA * H + 2 * NA + H + 1,
               "the flat gradient of obs_dim <= 16 fits one apply block");
-__global__ __launch_bounds__(NT_APPLY) void k_mlp_apply(SalpPpoAdam o, Layout L) {
+// c1, c2: 1 - beta1, 1 - beta2 as float32, from the launcher.
+__global__ __launch_bounds__(NT_APPLY) void k_mlp_apply(SalpPpoAdam o, Layout L, float c1, float c2) {
     __shared__ double sh[NT_APPLY / 64];
     __shared__ float s_coef;
     __shared__ float s_adam[2];   // lr / (1 - beta1^step), sqrt(1 - beta2^step)
@@ -687,8 +690,8 @@ __global__ __launch_bounds__(NT_APPLY) void k_mlp_apply(SalpPpoAdam o, Layout L)
         const int p = threadIdx.x + k * NT_APPLY;
         if (p < P) {
             const float gc = g[k] * coef;
-            const float m = b1 * m1[k] + (1.0f - b1) * gc;
-            const float v = b2 * v1[k] + (1.0f - b2) * gc * gc;
+            const float m = b1 * m1[k] + c1 * gc;
+            const float v = b2 * v1[k] + c2 * gc * gc;
             o.exp_avg[p] = m;
             o.exp_avg_sq[p] = v;
             *wp[k] = w1[k] - step_size * m / (sqrtf(v) / bc2_sqrt + eps);
@@ -724,7 +727,7 @@ __global__ __launch_bounds__(NT_ADAM) void k_mlp_norm(SalpPpoAdam o, int P) {
     if (threadIdx.x % 64 == 0 && p < P) o.workspace[p / 64] = q;
 }
 
-__global__ __launch_bounds__(NT_ADAM) void k_mlp_adam(SalpPpoAdam o, Layout L) {
+__global__ __launch_bounds__(NT_ADAM) void k_mlp_adam(SalpPpoAdam o, Layout L, float c1, float c2) {
     __shared__ float* s_base[SALP_MLP_N_TENSORS];   // params[t] - off[t]: p indexes it directly
     __shared__ int s_off[SALP_MLP_N_TENSORS];
     __shared__ float s_k[3];                        // clipping coefficient, lr / (1 - beta1^step), sqrt(1 - beta2^step)
@@ -783,8 +786,8 @@ __global__ __launch_bounds__(NT_ADAM) void k_mlp_adam(SalpPpoAdam o, Layout L) {
         const float w1 = *wp;
         const float coef = s_k[0], step_size = s_k[1], bc2_sqrt = s_k[2];
         const float gc = g * coef;
-        const float m = b1 * m1 + (1.0f - b1) * gc;
-        const float v = b2 * v1 + (1.0f - b2) * gc * gc;
+        const float m = b1 * m1 + c1 * gc;
+        const float v = b2 * v1 + c2 * gc * gc;
         o.exp_avg[p] = m;
         o.exp_avg_sq[p] = v;
         *wp = w1 - step_size * m / (sqrtf(v) / bc2_sqrt + eps);
@@ -846,12 +849,15 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t salp_ppo_mlp_adv_par
 extern "C" __attribute__((visibility("hidden"))) hipError_t salp_ppo_mlp_apply_launch(const SalpPpoAdam* o,
                                                                                        void* stream) {
     const Layout L = make_layout(o->obs_dim);
+    // 1 - beta in double, rounded once, as torch.optim.Adam passes it: formed in float32, 1.0f - (float)0.999 is
+    // 1.29e-5 below 0.001 and exp_avg_sq was that far from torch's (tests/test_gpu_ppo_mlp_ref.py)
+    const float c1 = (float)(1.0 - o->beta1), c2 = (float)(1.0 - o->beta2);
     if (o->workspace) {
         const int P = (int)L.off[SALP_MLP_N_TENSORS], nb = (P + NT_ADAM - 1) / NT_ADAM;
         if (!o->norm_ready) hipLaunchKernelGGL(k_mlp_norm, dim3(nb), dim3(NT_ADAM), 0, (hipStream_t)stream, *o, P);
-        hipLaunchKernelGGL(k_mlp_adam, dim3(nb), dim3(NT_ADAM), 0, (hipStream_t)stream, *o, L);
+        hipLaunchKernelGGL(k_mlp_adam, dim3(nb), dim3(NT_ADAM), 0, (hipStream_t)stream, *o, L, c1, c2);
     } else {
-        hipLaunchKernelGGL(k_mlp_apply, dim3(1), dim3(NT_APPLY), 0, (hipStream_t)stream, *o, L);
+        hipLaunchKernelGGL(k_mlp_apply, dim3(1), dim3(NT_APPLY), 0, (hipStream_t)stream, *o, L, c1, c2);
     }
     return hipGetLastError();
 }

@@ -10,5 +10,9 @@ without torch or a GPU):
   — drop-in replacements for the reference classes (src/salp_robot_env.py,
   src/robot.py).
 * :class:`grasp_lab_salp_amd.vec_env.SalpVecEnv` — SB3 VecEnv-shaped adapter.
+* :class:`grasp_lab_salp_amd.ppo.PPO`,
+  :class:`grasp_lab_salp_amd.recurrent_ppo.RecurrentPPO`,
+  :class:`grasp_lab_salp_amd.sac.SAC` — on-device learners (SAC is the one
+  src/train_robot.py trains with).
 """
 __version__ = "0.1.0"

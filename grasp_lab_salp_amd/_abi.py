@@ -6,7 +6,7 @@ drift apart silently.
 """
 import ctypes
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 # rows of salp_math_selftest's output (include/salp.h)
 MATH_SELFTEST_ROWS = 23
 MAX_OBSTACLES = 4

@@ -105,6 +105,93 @@ class SalpPpoAdam(ctypes.Structure):
     ]
 
 
+SAC_WORKSPACE_DOUBLES = 256   # include/salp.h SALP_SAC_WORKSPACE_DOUBLES
+
+
+class SalpReplay(ctypes.Structure):
+    _fields_ = [
+        ("capacity", ctypes.c_int64),
+        ("n_envs", ctypes.c_int64),
+        ("obs_dim", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("obs", ctypes.c_void_p),
+        ("next_obs", ctypes.c_void_p),
+        ("actions", ctypes.c_void_p),
+        ("rewards", ctypes.c_void_p),
+        ("dones", ctypes.c_void_p),
+        ("pos", ctypes.c_void_p),
+        ("size", ctypes.c_void_p),
+    ]
+
+
+class SalpReplayAdd(ctypes.Structure):
+    _fields_ = [
+        ("obs", ctypes.c_void_p),
+        ("actions", ctypes.c_void_p),
+        ("obs_after", ctypes.c_void_p),
+        ("terminal_obs", ctypes.c_void_p),
+        ("reward", ctypes.c_void_p),
+        ("terminated", ctypes.c_void_p),
+        ("truncated", ctypes.c_void_p),
+        ("diverged_obs_abs", ctypes.c_double),
+        ("diverged_reward_abs", ctypes.c_double),
+        ("diverged_out", ctypes.c_void_p),
+    ]
+
+
+class SalpReplaySample(ctypes.Structure):
+    _fields_ = [
+        ("batch", ctypes.c_int64),
+        ("seed", ctypes.c_uint64),
+        ("update", ctypes.c_void_p),
+        ("obs", ctypes.c_void_p),
+        ("next_obs", ctypes.c_void_p),
+        ("actions", ctypes.c_void_p),
+        ("rewards", ctypes.c_void_p),
+        ("dones", ctypes.c_void_p),
+        ("env_out", ctypes.c_void_p),
+        ("slot_out", ctypes.c_void_p),
+    ]
+
+
+class SalpSacTd(ctypes.Structure):
+    _fields_ = [
+        ("batch", ctypes.c_int64),
+        ("rewards", ctypes.c_void_p),
+        ("dones", ctypes.c_void_p),
+        ("q1_target", ctypes.c_void_p),
+        ("q2_target", ctypes.c_void_p),
+        ("logp_next", ctypes.c_void_p),
+        ("q1", ctypes.c_void_p),
+        ("q2", ctypes.c_void_p),
+        ("logp", ctypes.c_void_p),
+        ("log_alpha", ctypes.c_void_p),
+        ("gamma", ctypes.c_double),
+        ("target_entropy", ctypes.c_double),
+        ("workspace", ctypes.c_void_p),
+        ("target", ctypes.c_void_p),
+        ("dq1", ctypes.c_void_p),
+        ("dq2", ctypes.c_void_p),
+        ("out", ctypes.c_void_p),
+        ("alpha_used", ctypes.c_void_p),
+    ]
+
+
+class SalpSacPi(ctypes.Structure):
+    _fields_ = [
+        ("batch", ctypes.c_int64),
+        ("alpha_used", ctypes.c_void_p),
+        ("logp", ctypes.c_void_p),
+        ("q1_pi", ctypes.c_void_p),
+        ("q2_pi", ctypes.c_void_p),
+        ("workspace", ctypes.c_void_p),
+        ("out", ctypes.c_void_p),
+        ("dlogp", ctypes.c_void_p),
+        ("dq1", ctypes.c_void_p),
+        ("dq2", ctypes.c_void_p),
+    ]
+
+
 class SalpTraceBuffer(ctypes.Structure):
     _fields_ = [
         ("max_samples", ctypes.c_int64),
@@ -163,6 +250,13 @@ SIGNATURES = {
     "salp_ppo_mlp_grads": (ctypes.c_int, [ctypes.POINTER(SalpPpoMinibatch), _V]),
     "salp_ppo_mlp_apply": (ctypes.c_int, [ctypes.POINTER(SalpPpoAdam), _V]),
     "salp_ppo_mlp_adv_partials": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, _V, _V, _V, _V]),
+    "salp_replay_add": (ctypes.c_int, [ctypes.POINTER(SalpReplay), ctypes.POINTER(SalpReplayAdd), _V]),
+    "salp_replay_sample": (ctypes.c_int, [ctypes.POINTER(SalpReplay), ctypes.POINTER(SalpReplaySample), _V]),
+    "salp_sac_actor_head_forward": (ctypes.c_int, [ctypes.c_int64, _V, _V, _V, _V, _V, _V]),
+    "salp_sac_actor_head_backward": (ctypes.c_int, [ctypes.c_int64, _V, _V, _V, _V, _V, _V, _V, _V]),
+    "salp_sac_td_head": (ctypes.c_int, [ctypes.POINTER(SalpSacTd), _V]),
+    "salp_sac_pi_head": (ctypes.c_int, [ctypes.POINTER(SalpSacPi), _V]),
+    "salp_sac_polyak": (ctypes.c_int, [ctypes.c_int64, _V, _V, ctypes.c_double, _V]),
 }
 
 

@@ -2216,6 +2216,23 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t salp_gae_launch(
     const float* last_values, const float* last_dones, double gamma, double gae_lambda, float* advantages,
     float* returns, void* stream);
 
+extern "C" __attribute__((visibility("hidden"))) hipError_t salp_replay_add_launch(const SalpReplay* rb,
+                                                                                    const SalpReplayAdd* a,
+                                                                                    void* stream);
+extern "C" __attribute__((visibility("hidden"))) hipError_t salp_replay_sample_launch(const SalpReplay* rb,
+                                                                                       const SalpReplaySample* s,
+                                                                                       void* stream);
+extern "C" __attribute__((visibility("hidden"))) hipError_t salp_sac_actor_fwd_launch(
+    int64_t B, const float* mu, const float* log_std, const float* eps, float* act, float* logp, void* stream);
+extern "C" __attribute__((visibility("hidden"))) hipError_t salp_sac_actor_bwd_launch(
+    int64_t B, const float* log_std, const float* eps, const float* act, const float* da, const float* dlogp,
+    float* dmu, float* dls, void* stream);
+extern "C" __attribute__((visibility("hidden"))) hipError_t salp_sac_td_launch(const SalpSacTd* t, void* stream);
+extern "C" __attribute__((visibility("hidden"))) hipError_t salp_sac_pi_launch(const SalpSacPi* p, void* stream);
+extern "C" __attribute__((visibility("hidden"))) hipError_t salp_sac_polyak_launch(int64_t n, const float* params,
+                                                                                    float* target, double tau,
+                                                                                    void* stream);
+
 extern "C" {
 
 int salp_abi_version(void) { return SALP_ABI_VERSION; }
@@ -2727,6 +2744,69 @@ int salp_gae(int64_t n_steps, int64_t n_envs, const float* rewards, const float*
     const hipError_t e = salp_gae_launch(n_steps, n_envs, rewards, values, episode_starts, last_values, last_dones,
                                          gamma, gae_lambda, advantages, returns, stream);
     return check_hip(nullptr, e, "k_gae");
+}
+
+static bool replay_ok(const SalpReplay* rb) {
+    // row indices stay far inside int64: capacity x n_envs x obs_dim elements are allocated by the caller
+    return rb && rb->capacity > 0 && rb->n_envs > 0 && rb->obs_dim > 0 && rb->obs_dim <= SALP_OBS_DIM_MAX &&
+           rb->n_envs <= INT32_MAX && rb->obs && rb->next_obs && rb->actions && rb->rewards && rb->dones && rb->pos &&
+           rb->size;
+}
+
+int salp_replay_add(const SalpReplay* rb, const SalpReplayAdd* a, void* stream) {
+    if (!replay_ok(rb)) return fail(nullptr, SALP_EINVAL, "salp_replay_add: bad replay buffer");
+    if (!a || !a->obs || !a->actions || !a->obs_after || !a->terminal_obs || !a->reward || !a->terminated ||
+        !a->truncated)
+        return fail(nullptr, SALP_EINVAL, "salp_replay_add: null buffer");
+    return check_hip(nullptr, salp_replay_add_launch(rb, a, stream), "k_replay_add");
+}
+
+int salp_replay_sample(const SalpReplay* rb, const SalpReplaySample* s, void* stream) {
+    if (!replay_ok(rb)) return fail(nullptr, SALP_EINVAL, "salp_replay_sample: bad replay buffer");
+    if (!s || s->batch <= 0 || s->batch > (int64_t)1 << 32)   // the row index is a 32-bit Philox counter word
+        return fail(nullptr, SALP_EINVAL, "salp_replay_sample: batch must be in 1 .. 2^32");
+    if (!s->update || !s->obs || !s->next_obs || !s->actions || !s->rewards || !s->dones)
+        return fail(nullptr, SALP_EINVAL, "salp_replay_sample: null buffer");
+    return check_hip(nullptr, salp_replay_sample_launch(rb, s, stream), "k_replay_sample");
+}
+
+int salp_sac_actor_head_forward(int64_t batch, const float* mu, const float* log_std, const float* eps,
+                                float* act, float* logp, void* stream) {
+    if (batch <= 0) return fail(nullptr, SALP_EINVAL, "salp_sac_actor_head_forward: batch must be positive");
+    if (!mu || !log_std || !eps || !act || !logp)
+        return fail(nullptr, SALP_EINVAL, "salp_sac_actor_head_forward: null buffer");
+    return check_hip(nullptr, salp_sac_actor_fwd_launch(batch, mu, log_std, eps, act, logp, stream), "k_actor_fwd");
+}
+
+int salp_sac_actor_head_backward(int64_t batch, const float* log_std, const float* eps, const float* act,
+                                 const float* da, const float* dlogp, float* dmu, float* dls, void* stream) {
+    if (batch <= 0) return fail(nullptr, SALP_EINVAL, "salp_sac_actor_head_backward: batch must be positive");
+    if (!log_std || !eps || !act || !dmu || !dls)
+        return fail(nullptr, SALP_EINVAL, "salp_sac_actor_head_backward: null buffer");
+    return check_hip(nullptr, salp_sac_actor_bwd_launch(batch, log_std, eps, act, da, dlogp, dmu, dls, stream),
+                     "k_actor_bwd");
+}
+
+int salp_sac_td_head(const SalpSacTd* t, void* stream) {
+    if (!t || t->batch <= 0) return fail(nullptr, SALP_EINVAL, "salp_sac_td_head: batch must be positive");
+    if (!t->rewards || !t->dones || !t->q1_target || !t->q2_target || !t->logp_next || !t->q1 || !t->q2 || !t->logp ||
+        !t->log_alpha || !t->workspace || !t->target || !t->dq1 || !t->dq2 || !t->out || !t->alpha_used)
+        return fail(nullptr, SALP_EINVAL, "salp_sac_td_head: null buffer");
+    return check_hip(nullptr, salp_sac_td_launch(t, stream), "k_td");
+}
+
+int salp_sac_pi_head(const SalpSacPi* p, void* stream) {
+    if (!p || p->batch <= 0) return fail(nullptr, SALP_EINVAL, "salp_sac_pi_head: batch must be positive");
+    if (!p->alpha_used || !p->logp || !p->q1_pi || !p->q2_pi || !p->workspace || !p->out || !p->dlogp || !p->dq1 ||
+        !p->dq2)
+        return fail(nullptr, SALP_EINVAL, "salp_sac_pi_head: null buffer");
+    return check_hip(nullptr, salp_sac_pi_launch(p, stream), "k_pi");
+}
+
+int salp_sac_polyak(int64_t n, const float* params, float* target, double tau, void* stream) {
+    if (n <= 0 || !params || !target) return fail(nullptr, SALP_EINVAL, "salp_sac_polyak: bad argument");
+    if (!(tau >= 0 && tau <= 1)) return fail(nullptr, SALP_EINVAL, "salp_sac_polyak: tau must be in [0, 1]");
+    return check_hip(nullptr, salp_sac_polyak_launch(n, params, target, tau, stream), "k_polyak");
 }
 
 }  // extern "C"

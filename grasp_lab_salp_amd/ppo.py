@@ -2,7 +2,8 @@
 
 The reference trains with Stable-Baselines3 learners (SAC, src/train_robot.py:
 62-69; RecurrentPPO, src/train_robot_recurrent_ppo.py:85-107) on 4-8 envs
-stepped through Python processes.  Here the envs, the rollout buffer, the GAE
+stepped through Python processes; the SAC learner is sac.py, the recurrent
+one recurrent_ppo.py.  Here the envs, the rollout buffer, the GAE
 scan (HIP kernel ``salp_gae``) and the policy all stay in HBM:
 
 * collection: ``n_steps`` lock-step env-steps of every env (``salp_step`` with

@@ -1,0 +1,781 @@
+"""On-device SAC over the batched simulator: the learner of the reference's
+production training script, ``src/train_robot.py:62-69``
+(``SAC("MlpPolicy", vec_env, learning_rate=3e-4, buffer_size=100000,
+learning_starts=1000, batch_size=256, tau=0.005, gamma=0.99, train_freq=1,
+gradient_steps=1)``).
+
+Stable-Baselines3 (>= 2.0) is not installed here: its semantics are restated,
+and parity with it is unpinned.  What is kept:
+
+* policy: SB3's SAC ``MlpPolicy``: a 256-256 ReLU actor with a mean head and a
+  state-dependent log-std head (clamped to [-20, 2]), a tanh-squashed diagonal
+  Gaussian, two 256-256 ReLU Q-networks on ``cat(obs, action)`` and a target
+  copy of them; torch's default init, as SB3 uses for SAC;
+* the policy acts in [-1, 1]; the env receives the action unscaled to
+  ``Box([0, 0, -1], [1, 1, 1])`` and the replay buffer keeps the scaled one;
+* actions are uniform in the Box until ``learning_starts`` transitions;
+* the replay buffer holds ``max(buffer_size // n_envs, 1)`` slots per env;
+  ``next_obs`` is the terminal observation where an episode ended, and a
+  truncation does not cut the bootstrap (``handle_timeout_termination``);
+* ``ent_coef="auto"``: ``log_ent_coef`` starts at 0 with its own Adam and
+  ``target_entropy = -3``; the coefficient of before its step serves the whole
+  gradient step;
+* per gradient step: sample, actor(obs), [no grad] actor(next_obs) and the
+  target critics, critics(obs, a), TD head, critic Adam and alpha Adam,
+  critics(obs, a_pi), pi head, actor Adam, Polyak.
+
+The GEMMs are library calls through torch.  With ``fused=True`` (the default
+on a GPU) everything around them is the HIP kernels of csrc/salp_sac.hip
+(include/salp.h "SAC"): replay add / sample, the squashed-Gaussian head and
+its backward, the TD and pi heads with their gradients, and Polyak in one
+launch over flat parameter buffers.  ``fused=False`` runs the same step from
+the plain torch expressions below (``torch_squashed_gaussian``,
+``torch_td_head``, ``torch_pi_head``, index-op add / sample): the readable
+restatement, and the one that runs on the CPU.  Both draw the same batches.
+
+Collection is lock-step ``salp_step`` on a stream of its own, with the
+divergence guard, episode statistics and HIP-event phase timings of
+:class:`~grasp_lab_salp_amd.ppo.PPO`.  Not built: the actor inside the chained
+simulation kernel, HIP-graph capture of the step (the kernels read what
+changes per step from device memory, so they are ready for it), several GPUs,
+callbacks, save / load.
+"""
+import copy
+import ctypes
+import math
+
+import torch
+from torch import nn
+
+from . import _lib
+from .ppo import DIVERGED_OBS_ABS, DIVERGED_REWARD_ABS, diverged_mask, sampling_generator
+from ._abi import INFO, INFO_DIM
+
+__all__ = ["SAC", "SACPolicy", "ReplayBuffer", "squashed_gaussian", "td_head", "pi_head", "polyak",
+           "torch_squashed_gaussian", "torch_td_head", "torch_pi_head", "torch_polyak", "torch_replay_add",
+           "torch_replay_indices", "scale_action", "unscale_action", "critic_phase", "actor_phase",
+           "LOG_STD_MIN", "LOG_STD_MAX", "REPLAY_STREAM"]
+
+LOG_STD_MIN, LOG_STD_MAX = -20.0, 2.0     # SB3 sac/policies.py
+SQUASH_EPS = 1e-6                         # SB3 SquashedDiagGaussianDistribution.epsilon
+REPLAY_STREAM = 0x52504C59                # csrc/salp_sac.hip SP_STREAM_REPLAY
+_HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
+_EP_RETURN = INFO["ep_return"]
+_EP_LEN = INFO["ep_len"]
+
+
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr() if t is not None else 0)
+
+
+def _stream(dev):
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _f32(name, t, shape):
+    if not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: expected a float32 CUDA tensor of shape {tuple(shape)}, got "
+                         f"{t.dtype} {tuple(t.shape)} on {t.device}")
+    return t.contiguous()
+
+
+# ------------------------------------------------------------ action scaling
+def scale_action(action, low, high):
+    """SB3 ``BasePolicy.scale_action``: Box [low, high] -> [-1, 1]."""
+    return 2.0 * ((action - low) / (high - low)) - 1.0
+
+
+def unscale_action(scaled, low, high):
+    """SB3 ``BasePolicy.unscale_action``: [-1, 1] -> Box [low, high]."""
+    return low + 0.5 * (scaled + 1.0) * (high - low)
+
+
+# ------------------------------------------------- plain torch restatements
+def torch_squashed_gaussian(mu, log_std, eps):
+    """SB3 ``SquashedDiagGaussianDistribution`` of SAC's actor from the raw
+    log-std and N(0, 1) noise ``eps``: (action in [-1, 1], log-probability)."""
+    ls = torch.clamp(log_std, LOG_STD_MIN, LOG_STD_MAX)
+    a = torch.tanh(mu + ls.exp() * eps)
+    logp = (-0.5 * eps * eps - ls - _HALF_LOG_2PI).sum(-1) - torch.log(1.0 - a * a + SQUASH_EPS).sum(-1)
+    return a, logp
+
+
+def torch_td_head(rewards, dones, q1_target, q2_target, logp_next, q1, q2, logp, log_alpha, gamma, target_entropy):
+    """SB3 ``SAC.train``: (critic_loss, ent_coef_loss, target, alpha).  The
+    target and alpha carry no gradient; critic_loss is differentiable in q1,
+    q2 and ent_coef_loss in log_alpha ([1])."""
+    with torch.no_grad():
+        alpha = log_alpha.exp()
+        nq = torch.minimum(q1_target, q2_target) - alpha * logp_next
+        target = rewards + (1.0 - dones) * gamma * nq
+    critic_loss = 0.5 * (((q1 - target) ** 2).mean() + ((q2 - target) ** 2).mean())
+    ent_coef_loss = -(log_alpha * (logp.detach() + target_entropy)).mean()
+    return critic_loss, ent_coef_loss, target, alpha
+
+
+def torch_pi_head(alpha, logp, q1_pi, q2_pi):
+    """SB3 ``SAC.train``'s actor loss, mean(alpha logp - min(q1_pi, q2_pi));
+    ``torch.min`` over a dimension gives a tie's gradient to the first, q1."""
+    min_q = torch.min(torch.stack([q1_pi, q2_pi], dim=1), dim=1).values
+    return (alpha.detach() * logp - min_q).mean()
+
+
+def torch_polyak(params, targets, tau):
+    """SB3 ``polyak_update``: target = target (1 - tau) + tau param."""
+    with torch.no_grad():
+        for p, t in zip(params, targets):
+            t.mul_(1.0 - tau)
+            t.add_(p, alpha=tau)
+
+
+def _mulhilo(a, b):
+    """(high, low) 32-bit halves of a * b for a constant a < 2^32 and an int64
+    tensor b of values < 2^32, without leaving int64."""
+    bh, bl = b >> 16, b & 0xFFFF
+    ph, pl = a * bh, a * bl                     # < 2^48 each
+    hi = (ph + (pl >> 16)) >> 16
+    lo = (((ph & 0xFFFF) << 16) + pl) & 0xFFFFFFFF
+    return hi, lo
+
+
+def _philox4x32_10(c0, c1, c2, c3, k0, k1):
+    """Philox4x32-10 (csrc/salp_philox.h sp_philox4x32_10) on int64 tensors
+    holding 32-bit words; k0, k1 Python ints."""
+    m32 = 0xFFFFFFFF
+    for _ in range(10):
+        hi0, lo0 = _mulhilo(0xD2511F53, c0)
+        hi1, lo1 = _mulhilo(0xCD9E8D57, c2)
+        c0, c1, c2, c3 = hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0
+        k0, k1 = (k0 + 0x9E3779B9) & m32, (k1 + 0xBB67AE85) & m32
+    return c0, c1, c2, c3
+
+
+def torch_replay_indices(size, update, seed, batch):
+    """The (env, slot) draw of ``salp_replay_sample`` (include/salp.h) as torch
+    integer ops, without a host sync: ``size`` [n_envs] int64, ``update`` a
+    [1] int64 tensor, ``seed`` a Python int.  Bit-equal to the kernel."""
+    dev = size.device
+    n = size.numel()
+    u = update.reshape(1).to(torch.int64)
+    b = torch.arange(batch, dtype=torch.int64, device=dev)
+    zero = torch.zeros_like(b)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    v0, v1, _, _ = _philox4x32_10(zero + (u & 0xFFFFFFFF), zero + ((u >> 32) & 0xFFFFFFFF), b, zero + REPLAY_STREAM,
+                                  seed & 0xFFFFFFFF, seed >> 32)
+    env = (v0 * n) >> 32
+    # the first env at or after `env` (cyclically) that has stored something
+    ids = torch.arange(n, dtype=torch.int64, device=dev)
+    have = torch.where(size > 0, ids, torch.full_like(ids, 2 * n))
+    two = torch.cat([have, have + n])
+    nxt = torch.flip(torch.cummin(torch.flip(two, [0]), 0).values, [0])[:n]
+    env = torch.where(nxt[env] < 2 * n, nxt[env] % n, env)
+    slot = (v1 * size[env]) >> 32
+    return env, slot
+
+
+def torch_replay_add(rb, obs, actions, obs_after, terminal_obs, reward, terminated, truncated, guard=True):
+    """``salp_replay_add`` (include/salp.h) as torch index ops, without a host
+    sync; returns the diverged mask (bool [n_envs])."""
+    term = terminated.bool()
+    done = term | truncated.bool()
+    nxt = torch.where(done.unsqueeze(1), terminal_obs, obs_after)
+    rew = reward.to(torch.float32)
+    bad = diverged_mask(nxt, rew) if guard else torch.zeros_like(done)
+    keep = ~bad
+    env = torch.arange(rb.n_envs, device=obs.device)
+    p = rb.pos
+    for ring, new in ((rb.obs, obs), (rb.next_obs, nxt), (rb.actions, actions)):
+        ring[p, env] = torch.where(keep.unsqueeze(1), new.to(ring.dtype), ring[p, env])
+    rb.rewards[p, env] = torch.where(keep, rew.to(rb.rewards.dtype), rb.rewards[p, env])
+    rb.dones[p, env] = torch.where(keep, term.to(rb.dones.dtype), rb.dones[p, env])
+    rb.pos.copy_(torch.where(keep, (p + 1) % rb.capacity, p))
+    rb.size.copy_(torch.where(keep, torch.clamp(rb.size + 1, max=rb.capacity), rb.size))
+    return bad
+
+
+# ------------------------------------------------------ HIP-kernel wrappers
+class _ActorHeadFn(torch.autograd.Function):
+    """The squashed-Gaussian head through salp_sac_actor_head_forward /
+    _backward (include/salp.h): one kernel each way."""
+
+    @staticmethod
+    def forward(ctx, mu, log_std, eps):
+        B = mu.shape[0]
+        a = torch.empty_like(mu)
+        logp = torch.empty(B, dtype=mu.dtype, device=mu.device)
+        _lib.check(_lib.load().salp_sac_actor_head_forward(B, _ptr(mu), _ptr(log_std), _ptr(eps), _ptr(a),
+                                                           _ptr(logp), _stream(mu.device)))
+        ctx.save_for_backward(log_std, eps, a)
+        return a, logp
+
+    @staticmethod
+    def backward(ctx, da, dlogp):
+        log_std, eps, a = ctx.saved_tensors
+        da = None if da is None else da.contiguous()
+        dlogp = None if dlogp is None else dlogp.contiguous()
+        dmu, dls = torch.empty_like(a), torch.empty_like(a)
+        _lib.check(_lib.load().salp_sac_actor_head_backward(a.shape[0], _ptr(log_std), _ptr(eps), _ptr(a), _ptr(da),
+                                                            _ptr(dlogp), _ptr(dmu), _ptr(dls), _stream(a.device)))
+        return dmu, dls, None
+
+
+def squashed_gaussian(mu, log_std, eps):
+    """Fused :func:`torch_squashed_gaussian` (differentiable in mu, log_std);
+    float32 CUDA tensors [B, 3]."""
+    shape = (mu.shape[0], 3)
+    return _ActorHeadFn.apply(_f32("mu", mu, shape), _f32("log_std", log_std, shape), _f32("eps", eps, shape))
+
+
+def td_head(rewards, dones, q1_target, q2_target, logp_next, q1, q2, logp, log_alpha, gamma, target_entropy):
+    """``salp_sac_td_head``: (out [3] = critic_loss, ent_coef_loss,
+    d ent_coef_loss / d log_alpha; target [B]; dq1, dq2 [B] = d critic_loss /
+    d q; alpha_used [1]).  No autograd: the caller feeds dq into backward."""
+    B = rewards.shape[0]
+    rows = [_f32(n, t.detach(), (B,)) for n, t in (("rewards", rewards), ("dones", dones), ("q1_target", q1_target),
+                                                   ("q2_target", q2_target), ("logp_next", logp_next), ("q1", q1),
+                                                   ("q2", q2), ("logp", logp))]
+    la = _f32("log_alpha", log_alpha.detach(), (1,))
+    dev = rewards.device
+    new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)  # noqa: E731
+    target, dq1, dq2, out, alpha = new(B), new(B), new(B), new(3), new(1)
+    ws = torch.empty(_lib.SAC_WORKSPACE_DOUBLES, dtype=torch.float64, device=dev)
+    t = _lib.SalpSacTd(B, *(r.data_ptr() for r in rows), la.data_ptr(), float(gamma), float(target_entropy),
+                       ws.data_ptr(), target.data_ptr(), dq1.data_ptr(), dq2.data_ptr(), out.data_ptr(),
+                       alpha.data_ptr())
+    _lib.check(_lib.load().salp_sac_td_head(ctypes.byref(t), _stream(dev)))
+    return out, target, dq1, dq2, alpha
+
+
+def pi_head(alpha_used, logp, q1_pi, q2_pi):
+    """``salp_sac_pi_head``: (out [1] = actor_loss; dlogp, dq1, dq2 [B] = its
+    gradient in logp, q1_pi, q2_pi).  No autograd, as :func:`td_head`."""
+    B = logp.shape[0]
+    al = _f32("alpha_used", alpha_used.detach(), (1,))
+    rows = [_f32(n, t.detach(), (B,)) for n, t in (("logp", logp), ("q1_pi", q1_pi), ("q2_pi", q2_pi))]
+    dev = logp.device
+    new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)  # noqa: E731
+    out, dlogp, dq1, dq2 = new(1), new(B), new(B), new(B)
+    ws = torch.empty(_lib.SAC_WORKSPACE_DOUBLES, dtype=torch.float64, device=dev)
+    p = _lib.SalpSacPi(B, al.data_ptr(), *(r.data_ptr() for r in rows), ws.data_ptr(), out.data_ptr(),
+                       dlogp.data_ptr(), dq1.data_ptr(), dq2.data_ptr())
+    _lib.check(_lib.load().salp_sac_pi_head(ctypes.byref(p), _stream(dev)))
+    return out, dlogp, dq1, dq2
+
+
+def polyak(params_flat, target_flat, tau):
+    """``salp_sac_polyak`` in place on ``target_flat`` (flat float32 CUDA vectors)."""
+    n = params_flat.numel()
+    for name, t in (("params_flat", params_flat), ("target_flat", target_flat)):
+        if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 1 or t.numel() != n or not t.is_contiguous():
+            raise ValueError(f"polyak: {name} must be a contiguous flat float32 CUDA vector of {n} elements")
+    _lib.check(_lib.load().salp_sac_polyak(n, _ptr(params_flat), _ptr(target_flat), float(tau),
+                                           _stream(target_flat.device)))
+    return target_flat
+
+
+# ------------------------------------------------------------- replay buffer
+class ReplayBuffer:
+    """SB3 ``ReplayBuffer`` in device memory: rings [capacity, n_envs, ...]
+    with ``capacity = max(buffer_size // n_envs, 1)`` and per-env cursors
+    ``pos`` / ``size`` (an env whose step diverged stores nothing, so the
+    cursors differ between envs and the rings have no holes).  ``fused``:
+    the HIP kernels ``salp_replay_add`` / ``salp_replay_sample`` (CUDA only),
+    else torch index ops; both store and draw the same rows."""
+
+    def __init__(self, buffer_size, n_envs, obs_dim, device, act_dim=3, seed=0, fused=None, dtype=torch.float32):
+        if act_dim != 3:
+            raise ValueError("the replay kernels store the simulator's 3 action dimensions")
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.fused = self.device.type == "cuda" if fused is None else bool(fused)
+        if self.fused and (self.device.type != "cuda" or dtype != torch.float32):
+            raise ValueError("fused=True runs HIP kernels: it needs a ROCm GPU device and float32")
+        self.n_envs, self.obs_dim = int(n_envs), int(obs_dim)
+        self.capacity = max(int(buffer_size) // self.n_envs, 1)
+        self.seed = int(seed)
+        z = lambda *s: torch.zeros(s, dtype=dtype, device=self.device)  # noqa: E731
+        c, n = self.capacity, self.n_envs
+        self.obs, self.next_obs = z(c, n, self.obs_dim), z(c, n, self.obs_dim)
+        self.actions, self.rewards, self.dones = z(c, n, 3), z(c, n), z(c, n)
+        self.pos = torch.zeros(n, dtype=torch.int64, device=self.device)
+        self.size = torch.zeros(n, dtype=torch.int64, device=self.device)
+        self._c = None
+        if self.fused:
+            self._c = _lib.SalpReplay(c, n, self.obs_dim, 0, self.obs.data_ptr(), self.next_obs.data_ptr(),
+                                      self.actions.data_ptr(), self.rewards.data_ptr(), self.dones.data_ptr(),
+                                      self.pos.data_ptr(), self.size.data_ptr())
+
+    def add(self, obs, actions, obs_after, terminal_obs, reward, terminated, truncated, guard=True, diverged_out=None):
+        """One env-step of every env (what ``BatchedSalpEnv.step(auto_reset=
+        True, out=...)`` wrote: fp64 reward, u8 flags).  Returns the diverged
+        mask (u8 [n_envs] when fused, else bool), written to ``diverged_out``
+        when given."""
+        if not self.fused:
+            bad = torch_replay_add(self, obs, actions, obs_after, terminal_obs, reward, terminated, truncated, guard)
+            if diverged_out is not None:
+                diverged_out.copy_(bad)
+                return diverged_out
+            return bad
+        n, D = self.n_envs, self.obs_dim
+        for name, t, shape, dt in (("obs", obs, (n, D), torch.float32), ("actions", actions, (n, 3), torch.float32),
+                                   ("obs_after", obs_after, (n, D), torch.float32),
+                                   ("terminal_obs", terminal_obs, (n, D), torch.float32),
+                                   ("reward", reward, (n,), torch.float64),
+                                   ("terminated", terminated, (n,), torch.uint8),
+                                   ("truncated", truncated, (n,), torch.uint8)):
+            if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f"ReplayBuffer.add: {name!r} must be a contiguous {dt} tensor of shape {shape} on "
+                                 f"{self.device}")
+        if diverged_out is None:
+            diverged_out = torch.empty(n, dtype=torch.uint8, device=self.device)
+        a = _lib.SalpReplayAdd(obs.data_ptr(), actions.data_ptr(), obs_after.data_ptr(), terminal_obs.data_ptr(),
+                               reward.data_ptr(), terminated.data_ptr(), truncated.data_ptr(),
+                               DIVERGED_OBS_ABS if guard else 0.0, DIVERGED_REWARD_ABS if guard else 0.0,
+                               diverged_out.data_ptr())
+        _lib.check(_lib.load().salp_replay_add(ctypes.byref(self._c), ctypes.byref(a), _stream(self.device)))
+        return diverged_out
+
+    def sample(self, batch_size, update, return_indices=False):
+        """``batch_size`` transitions (obs, actions, next_obs, rewards, dones)
+        drawn for gradient step ``update`` (a [1] int64 device tensor: a
+        replayed graph sees its new value).  At least one env must have stored
+        a transition.  ``return_indices``: also the (env, slot) pairs."""
+        B = int(batch_size)
+        if not self.fused:
+            env, slot = torch_replay_indices(self.size, update, self.seed, B)
+            out = (self.obs[slot, env], self.actions[slot, env], self.next_obs[slot, env], self.rewards[slot, env],
+                   self.dones[slot, env])
+            return out + ((env, slot) if return_indices else ())
+        if update.dtype != torch.int64 or update.numel() != 1 or update.device != self.device:
+            raise ValueError("ReplayBuffer.sample: update must be a one-element int64 tensor on the buffer's device")
+        new = lambda *s: torch.empty(s, dtype=torch.float32, device=self.device)  # noqa: E731
+        obs, nxt, act, rew, done = new(B, self.obs_dim), new(B, self.obs_dim), new(B, 3), new(B), new(B)
+        env = slot = None
+        if return_indices:
+            env = torch.empty(B, dtype=torch.int64, device=self.device)
+            slot = torch.empty(B, dtype=torch.int64, device=self.device)
+        s = _lib.SalpReplaySample(B, self.seed & 0xFFFFFFFFFFFFFFFF, update.data_ptr(), obs.data_ptr(),
+                                  nxt.data_ptr(), act.data_ptr(), rew.data_ptr(), done.data_ptr(),
+                                  env.data_ptr() if return_indices else None,
+                                  slot.data_ptr() if return_indices else None)
+        _lib.check(_lib.load().salp_replay_sample(ctypes.byref(self._c), ctypes.byref(s), _stream(self.device)))
+        return (obs, act, nxt, rew, done) + ((env, slot) if return_indices else ())
+
+
+# -------------------------------------------------------------------- policy
+def _mlp(d_in, hidden, d_out=None):
+    layers, d = [], d_in
+    for h in hidden:
+        layers += [nn.Linear(d, h), nn.ReLU()]
+        d = h
+    if d_out is not None:
+        layers.append(nn.Linear(d, d_out))
+    return nn.Sequential(*layers)
+
+
+class _Actor(nn.Module):
+    def __init__(self, obs_dim, act_dim, hidden):
+        super().__init__()
+        self.latent_pi = _mlp(obs_dim, hidden)
+        self.mu = nn.Linear(hidden[-1], act_dim)
+        self.log_std = nn.Linear(hidden[-1], act_dim)
+
+    def forward(self, obs):
+        """(mean, raw log-std); the heads clamp the log-std."""
+        z = self.latent_pi(obs)
+        return self.mu(z), self.log_std(z)
+
+
+class _Critic(nn.Module):
+    """SB3 ``ContinuousCritic`` with n_critics = 2.  After :meth:`flatten_`
+    every parameter is a view into ``flat``, so Polyak is one launch."""
+
+    def __init__(self, obs_dim, act_dim, hidden):
+        super().__init__()
+        self.qf0 = _mlp(obs_dim + act_dim, hidden, 1)
+        self.qf1 = _mlp(obs_dim + act_dim, hidden, 1)
+        self.flat = None
+
+    def forward(self, obs, action):
+        x = torch.cat([obs, action], dim=1)
+        return self.qf0(x).squeeze(-1), self.qf1(x).squeeze(-1)
+
+    def flatten_(self):
+        ps = list(self.parameters())
+        flat = torch.cat([p.detach().reshape(-1) for p in ps])
+        off = 0
+        for p in ps:
+            p.data = flat[off:off + p.numel()].view_as(p)
+            off += p.numel()
+        self.flat = flat
+        return self
+
+    def is_flat(self):
+        if self.flat is None:
+            return False
+        off = 0
+        for p in self.parameters():
+            if p.data_ptr() != self.flat.data_ptr() + off * self.flat.element_size() or not p.is_contiguous():
+                return False
+            off += p.numel()
+        return off == self.flat.numel()
+
+
+class SACPolicy(nn.Module):
+    """SB3's SAC ``MlpPolicy`` (``net_arch=[256, 256]``, ReLU, two critics, a
+    target copy of the critics; torch's default init).  Built on ``device``:
+    the critics' parameters are views into one flat buffer each (``critic.flat``,
+    ``critic_target.flat``); after moving or copying the module call
+    :meth:`flatten_` again."""
+
+    def __init__(self, obs_dim, act_dim=3, hidden=(256, 256), device=None):
+        super().__init__()
+        self.obs_dim, self.act_dim = int(obs_dim), int(act_dim)
+        self.actor = _Actor(obs_dim, act_dim, hidden)
+        self.critic = _Critic(obs_dim, act_dim, hidden)
+        self.critic_target = copy.deepcopy(self.critic)
+        for p in self.critic_target.parameters():
+            p.requires_grad_(False)
+        if device is not None:
+            self.to(device)
+        self.flatten_()
+
+    def flatten_(self):
+        self.critic.flatten_()
+        self.critic_target.flatten_()
+        return self
+
+    def forward(self, obs, eps=None):
+        """Action in [-1, 1]: the mean's tanh (deterministic), or a sample with noise ``eps``."""
+        mu, log_std = self.actor(obs)
+        if eps is None:
+            return torch.tanh(mu)
+        return torch_squashed_gaussian(mu, log_std, eps)[0]
+
+
+# ------------------------------------------------------------- gradient step
+def critic_phase(policy, log_alpha, batch, eps_pi, eps_next, gamma, target_entropy, fused):
+    """First half of SB3 ``SAC.train``'s gradient step, up to the backward of
+    the critic and entropy-coefficient losses (no optimizer step).  The
+    critics' gradients are added to their ``.grad`` as autograd does;
+    ``log_alpha.grad`` is overwritten with this batch's gradient on both paths.  ``batch`` = (obs,
+    actions, next_obs, rewards, dones); ``eps_*`` [B, 3] N(0, 1) noise for the
+    actions at obs and next_obs.  Returns what :func:`actor_phase` needs."""
+    obs, act, next_obs, rew, done = batch
+    head = squashed_gaussian if fused else torch_squashed_gaussian
+    a_pi, logp = head(*policy.actor(obs), eps_pi)
+    with torch.no_grad():
+        a_next, logp_next = head(*policy.actor(next_obs), eps_next)
+        q1t, q2t = policy.critic_target(next_obs, a_next)
+    q1, q2 = policy.critic(obs, act)
+    if fused:
+        out, target, dq1, dq2, alpha = td_head(rew, done, q1t, q2t, logp_next, q1, q2, logp, log_alpha, gamma,
+                                               target_entropy)
+        torch.autograd.backward((q1, q2), (dq1, dq2))
+        if log_alpha.requires_grad:
+            log_alpha.grad = out[2:3]
+        critic_loss, ent_coef_loss = out[0], out[1]
+    else:
+        critic_loss, ent_coef_loss, target, alpha = torch_td_head(rew, done, q1t, q2t, logp_next, q1, q2, logp,
+                                                                  log_alpha, gamma, target_entropy)
+        log_alpha.grad = None   # as the fused branch: this batch's gradient alone, never a running sum
+        (critic_loss + ent_coef_loss if log_alpha.requires_grad else critic_loss).backward()
+        critic_loss, ent_coef_loss = critic_loss.detach(), ent_coef_loss.detach()
+    return {"obs": obs, "a_pi": a_pi, "logp": logp, "alpha": alpha, "target": target,
+            "critic_loss": critic_loss, "ent_coef_loss": ent_coef_loss}
+
+
+def actor_phase(policy, st, fused):
+    """Second half: critics(obs, a_pi), the actor loss and its backward into
+    the actor's parameters only (SB3 lets it reach the critics too and zeroes
+    those gradients before their next step).  Returns the actor loss."""
+    q1_pi, q2_pi = policy.critic(st["obs"], st["a_pi"])
+    params = list(policy.actor.parameters())
+    if fused:
+        out, dlogp, dq1, dq2 = pi_head(st["alpha"], st["logp"], q1_pi, q2_pi)
+        torch.autograd.backward((q1_pi, q2_pi, st["logp"]), (dq1, dq2, dlogp), inputs=params)
+        return out[0]
+    loss = torch_pi_head(st["alpha"], st["logp"], q1_pi, q2_pi)
+    loss.backward(inputs=params)
+    return loss.detach()
+
+
+# ------------------------------------------------------------------- learner
+class SAC:
+    """SB3-style SAC on a :class:`~grasp_lab_salp_amd.vec_env.SalpVecEnv` (or
+    anything exposing ``.sim`` = :class:`BatchedSalpEnv`).  Constructor
+    arguments and defaults follow SB3's ``SAC``; every keyword of
+    ``src/train_robot.py:62-69`` is accepted.
+
+    ``train_freq``: lock-step env-steps (of all envs) between updates, an int
+    or ``(n, "step")``; ``gradient_steps=-1``: as many gradient steps as
+    transitions collected.  ``ent_coef``: ``"auto"``, ``"auto_<init>"`` or a
+    fixed value.  ``fused``: HIP kernels around the GEMMs (default on a GPU) or
+    plain torch.  ``tensorboard_log`` is accepted and unused (``history`` holds
+    the rows a logger would get); ``device`` other than ``None`` / ``"auto"``
+    must be the simulator's device.  ``seed`` seeds the policy's init (without
+    moving the process-wide generator), the exploration noise and the sampler.
+    One GPU only."""
+
+    def __init__(self, policy, env, learning_rate=3e-4, buffer_size=1_000_000, learning_starts=100, batch_size=256,
+                 tau=0.005, gamma=0.99, train_freq=1, gradient_steps=1, ent_coef="auto", target_entropy="auto",
+                 seed=0, fused=None, verbose=0, tensorboard_log=None, device="auto", reset_nonfinite=True):
+        if policy not in ("MlpPolicy", None) and not isinstance(policy, SACPolicy):
+            raise ValueError("policy must be 'MlpPolicy' or a SACPolicy")
+        self.env = env
+        self.sim = getattr(env, "sim", env)
+        self.device = torch.device(self.sim.device)
+        if device not in (None, "auto") and torch.device(device).type != self.device.type:
+            raise ValueError(f"device={device!r}: the learner runs on the simulator's device, {self.device}")
+        self.n_envs, self.obs_dim, self.act_dim = int(self.sim.n_envs), int(self.sim.obs_dim), 3
+        on_gpu = self.device.type == "cuda"
+        if fused and not on_gpu:
+            raise ValueError("fused=True runs HIP kernels: it needs a ROCm GPU device")
+        self.fused = on_gpu if fused is None else bool(fused)
+        if isinstance(train_freq, (tuple, list)):
+            if len(train_freq) != 2 or train_freq[1] not in ("step", "steps"):
+                raise ValueError("train_freq: an int or (n, 'step'); episode-based collection is not built")
+            train_freq = train_freq[0]
+        self.train_freq, self.gradient_steps = int(train_freq), int(gradient_steps)
+        if self.train_freq < 1:
+            raise ValueError("train_freq must be >= 1")
+        self.learning_rate, self.learning_starts = float(learning_rate), int(learning_starts)
+        self.batch_size, self.tau, self.gamma = int(batch_size), float(tau), float(gamma)
+        self.verbose, self.tensorboard_log, self.reset_nonfinite = verbose, tensorboard_log, bool(reset_nonfinite)
+        self.seed = int(seed)
+        if isinstance(policy, SACPolicy):
+            self.policy = policy
+        else:
+            # the init draws come from the global CPU generator seeded with `seed`, inside a fork:
+            # building a learner leaves the process-wide generator where it was
+            with torch.random.fork_rng(devices=[]):
+                torch.manual_seed(self.seed)
+                self.policy = SACPolicy(self.obs_dim, self.act_dim, device=self.device)
+        if self.fused and not (self.policy.critic.is_flat() and self.policy.critic_target.is_flat()):
+            raise ValueError("the critics' parameters must be views into their flat buffers: SACPolicy.flatten_()")
+        self.target_entropy = -float(self.act_dim) if target_entropy == "auto" else float(target_entropy)
+        init, auto = 1.0, isinstance(ent_coef, str)
+        if auto:
+            if not ent_coef.startswith("auto"):
+                raise ValueError("ent_coef: 'auto', 'auto_<initial value>' or a float")
+            if "_" in ent_coef:
+                init = float(ent_coef.split("_")[1])
+        else:
+            init = float(ent_coef)
+        if not init > 0:
+            raise ValueError("the entropy coefficient must be positive")
+        self.log_ent_coef = torch.full((1,), math.log(init), dtype=torch.float32, device=self.device,
+                                       requires_grad=auto)
+        adam = lambda ps: torch.optim.Adam(ps, lr=self.learning_rate, fused=on_gpu or None)  # noqa: E731
+        self.actor_opt = adam(self.policy.actor.parameters())
+        self.critic_opt = adam(self.policy.critic.parameters())
+        self.ent_coef_opt = adam([self.log_ent_coef]) if auto else None
+        self.sample_gen = sampling_generator(self.seed, self.device)
+        self.replay = ReplayBuffer(buffer_size, self.n_envs, self.obs_dim, self.device, seed=self.seed,
+                                   fused=self.fused)
+        self.low = torch.tensor([0.0, 0.0, -1.0], device=self.device)
+        self.high = torch.tensor([1.0, 1.0, 1.0], device=self.device)
+        self._update = torch.zeros(1, dtype=torch.int64, device=self.device)   # gradient steps so far
+        self._obs = None
+        self._out = None
+        self._nonfinite = torch.zeros((), dtype=torch.int64, device=self.device)
+        self._ep_stats = torch.zeros(4, dtype=torch.float64, device=self.device)
+        self._loss_acc = torch.zeros(4, dtype=torch.float32, device=self.device)
+        self._collect_stream = None
+        self._events = []
+        self.num_timesteps = 0
+        self.n_updates = 0
+        self.logger = {}
+        self.timing = {"collect_s": 0.0, "sample_s": 0.0, "update_s": 0.0}
+        self.history = []
+
+    # -------------------------------------------------------- collection
+    def _step_out(self):
+        """Two sets of step outputs, used in turn: the observation the next
+        action is taken on stays valid while the step after it is written."""
+        if self._out is None:
+            n, od, dev = self.n_envs, self.obs_dim, self.device
+            mk = lambda: {"obs": torch.empty((n, od), dtype=torch.float32, device=dev),  # noqa: E731
+                          "reward": torch.empty(n, dtype=torch.float64, device=dev),
+                          "terminated": torch.empty(n, dtype=torch.uint8, device=dev),
+                          "truncated": torch.empty(n, dtype=torch.uint8, device=dev),
+                          "terminal_obs": torch.empty((n, od), dtype=torch.float32, device=dev),
+                          "info": torch.empty((n, INFO_DIM), dtype=torch.float64, device=dev)}
+            self._out = [mk(), mk()]
+        self._out.reverse()
+        return self._out[0]
+
+    @torch.no_grad()
+    def _sample_action(self, obs):
+        """The scaled action in [-1, 1]: uniform until learning_starts, then the policy's sample."""
+        if self.num_timesteps < self.learning_starts:
+            return 2.0 * torch.rand((self.n_envs, 3), generator=self.sample_gen, device=self.device) - 1.0
+        eps = torch.randn((self.n_envs, 3), generator=self.sample_gen, device=self.device)
+        head = squashed_gaussian if self.fused else torch_squashed_gaussian
+        return head(*self.policy.actor(obs), eps)[0]
+
+    def collect_step(self):
+        """One lock-step env-step of every env into the replay buffer."""
+        sim = self.sim
+        if self._obs is None:
+            self._obs = sim.reset()
+        obs = self._obs
+        a = self._sample_action(obs).contiguous()
+        r = sim.step(unscale_action(a, self.low, self.high), auto_reset=True, out=self._step_out())
+        bad = self.replay.add(obs, a, r.obs, r.terminal_obs, r.reward, r.terminated, r.truncated,
+                              guard=self.reset_nonfinite).bool()
+        done = (r.terminated | r.truncated).bool()
+        if self.reset_nonfinite:
+            # as PPO._reset_diverged: a diverged env that did not end its episode is reset on the spot
+            self._nonfinite += bad.sum()
+            again = bad & ~done
+            fresh = sim.reset(mask=again)
+            r.obs.copy_(torch.where(again.unsqueeze(1), fresh, r.obs))
+        ended = done & ~bad
+        ep_ret, ep_len = r.info[:, _EP_RETURN], r.info[:, _EP_LEN]
+        zero = torch.zeros_like(ep_ret)
+        self._ep_stats += torch.stack([torch.where(ended, ep_ret, zero).sum(), ended.sum().double(),
+                                       (ended & r.terminated.bool()).sum().double(),
+                                       torch.where(ended, ep_len, zero).sum()])
+        self._obs = r.obs
+        self.num_timesteps += self.n_envs
+
+    @property
+    def nonfinite_resets(self):
+        """Envs whose transition was dropped because their state diverged (host int; syncs)."""
+        return int(self._nonfinite)
+
+    # ------------------------------------------------------------ update
+    def _noise(self):
+        return torch.randn((self.batch_size, 3), generator=self.sample_gen, device=self.device)
+
+    def gradient_step(self, batch):
+        """One SB3 ``SAC.train`` gradient step on ``batch`` (see the module
+        docstring for the order); adds the losses to the running sums."""
+        pol = self.policy
+        self.critic_opt.zero_grad(set_to_none=True)
+        self.actor_opt.zero_grad(set_to_none=True)
+        if self.ent_coef_opt is not None:
+            self.ent_coef_opt.zero_grad(set_to_none=True)
+        st = critic_phase(pol, self.log_ent_coef, batch, self._noise(), self._noise(), self.gamma,
+                          self.target_entropy, self.fused)
+        self.critic_opt.step()
+        if self.ent_coef_opt is not None:
+            self.ent_coef_opt.step()
+        actor_loss = actor_phase(pol, st, self.fused)
+        self.actor_opt.step()
+        if self.fused:
+            polyak(pol.critic.flat, pol.critic_target.flat, self.tau)
+        else:
+            torch_polyak(pol.critic.parameters(), pol.critic_target.parameters(), self.tau)
+        self._loss_acc += torch.stack([st["critic_loss"], actor_loss, st["ent_coef_loss"], st["alpha"][0]])
+        self._update += 1
+        self.n_updates += 1
+
+    def train(self, gradient_steps, events=None):
+        """``gradient_steps`` times: sample a batch, one gradient step.
+        ``events``: a list that receives three HIP events of the first step,
+        all on the stream the update runs on (before the sample, between the
+        sample and the update, after the update), for the phase timings."""
+        for k in range(gradient_steps):
+            ev = events if (events is not None and k == 0) else None
+            if ev is not None:
+                ev.append(self._event())
+            batch = self.replay.sample(self.batch_size, self._update)
+            if ev is not None:
+                ev.append(self._event())
+            self.gradient_step(batch)
+            if ev is not None:
+                ev.append(self._event())
+
+    def _event(self):
+        e = torch.cuda.Event(enable_timing=True)
+        e.record(torch.cuda.current_stream(self.device))
+        return e
+
+    def _drain_events(self):
+        """Resolve the recorded phase events into ``timing`` (synchronises)."""
+        if not self._events:
+            return
+        self._events[-1][0][-1].synchronize()
+        for ev, steps in self._events:
+            self.timing["collect_s"] += ev[0].elapsed_time(ev[1]) / 1e3
+            if len(ev) == 5:   # the first gradient step of the iteration stands for all of them
+                self.timing["sample_s"] += ev[2].elapsed_time(ev[3]) / 1e3 * steps
+                self.timing["update_s"] += ev[3].elapsed_time(ev[4]) / 1e3 * steps
+        self._events = []
+
+    def learn(self, total_timesteps, callback=None, tb_log_name=None, progress_bar=False, log_interval=100):
+        """Collect ``train_freq`` env-steps, then train, until ``total_timesteps``
+        transitions.  ``callback``, ``tb_log_name`` and ``progress_bar`` are
+        accepted for SB3's signature and unused (callbacks are not built).
+        Every ``log_interval`` iterations the phase timings (HIP events: the
+        collection on its stream; the first gradient step's sample and update
+        on the update's stream, after it has waited for the collection, scaled
+        by the number of gradient steps) and a ``history`` row are resolved;
+        that is the only host synchronisation."""
+        gpu = self.device.type == "cuda"
+        if gpu and self._collect_stream is None:
+            self._collect_stream = torch.cuda.Stream(self.device)
+        start = self.num_timesteps
+        it = 0
+        while self.num_timesteps - start < total_timesteps:
+            ev = None
+            if gpu:
+                # the collection's eager GEMMs stay off the stream the update runs on (DESIGN.md §5 "HIP graphs")
+                stream, cs = torch.cuda.current_stream(self.device), self._collect_stream
+                cs.wait_stream(stream)
+                with torch.cuda.stream(cs):
+                    ev = [self._event()]
+                    for _ in range(self.train_freq):
+                        self.collect_step()
+                    ev.append(self._event())
+                stream.wait_stream(cs)
+            else:
+                for _ in range(self.train_freq):
+                    self.collect_step()
+            steps = 0
+            if self.num_timesteps > self.learning_starts:
+                steps = self.gradient_steps if self.gradient_steps >= 0 else self.train_freq * self.n_envs
+                self.train(steps, ev)
+            if ev is not None:
+                self._events.append((ev, steps))
+            it += 1
+            logged = it % max(int(log_interval), 1) == 0
+            if logged:
+                self._log()
+        if it and not logged:
+            self._log()
+        return self
+
+    def _log(self):
+        self._drain_events()
+        ret_sum, n_ep, n_succ, len_sum = self._ep_stats.tolist()
+        k = max(self.n_updates - self.logger.get("n_updates", 0), 1)
+        cl, al, el, ec = (self._loss_acc / k).tolist()
+        self._loss_acc.zero_()
+        self._ep_stats.zero_()
+        self.logger = {"timesteps": self.num_timesteps, "n_updates": self.n_updates, "critic_loss": cl,
+                       "actor_loss": al, "ent_coef_loss": el, "ent_coef": ec, "episodes": int(n_ep),
+                       "ep_return_mean": ret_sum / n_ep if n_ep else None,
+                       "success_rate": n_succ / n_ep if n_ep else None,
+                       "ep_len_mean": len_sum / n_ep if n_ep else None, "diverged_envs": self.nonfinite_resets}
+        self.history.append(self.logger)
+        if self.verbose:
+            print(self.logger, flush=True)
+
+    # ----------------------------------------------------------- predict
+    @torch.no_grad()
+    def predict(self, observation, state=None, episode_start=None, deterministic=True):
+        """SB3 ``predict``: (action in the env's Box, None).  A NumPy
+        observation gives a NumPy action; one observation gives one action."""
+        as_numpy = not torch.is_tensor(observation)
+        obs = torch.as_tensor(observation, dtype=torch.float32, device=self.device)
+        single = obs.dim() == 1
+        obs = obs.reshape(-1, self.obs_dim)
+        eps = None if deterministic else torch.randn((obs.shape[0], 3), generator=self.sample_gen,
+                                                      device=self.device)
+        a = unscale_action(self.policy(obs, eps), self.low, self.high)
+        a = a[0] if single else a
+        return (a.cpu().numpy() if as_numpy else a), None

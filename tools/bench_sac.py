@@ -1,0 +1,75 @@
+"""The on-device SAC learner (grasp_lab_salp_amd/sac.py), fused and plain.
+
+    python tools/bench_sac.py [--iters 300] [--warmup 30] [--configs ref,wide]
+
+Prints one JSON line.  Per configuration and for ``fused`` on and off: full
+iteration env-steps/s (collection + sample + update, host clock around a
+device synchronise) and the milliseconds per iteration of each phase (HIP
+events: the collection, and the first gradient step's sample and update).
+
+  ref   8 envs with the settings of src/train_robot.py:62-69 (buffer 100 000,
+        batch 256, train_freq 1, gradient_steps 1)
+  wide  4 096 envs, batch_size 4 096, gradient_steps 1
+
+learning_starts is one env-step, so every timed iteration trains; the warm-up
+iterations (untimed) fill the buffer and load the GEMMs' kernels.  The
+fused / plain ratio is reported, not judged.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+CONFIGS = {"ref": dict(n_envs=8, batch_size=256, buffer_size=100000),
+           "wide": dict(n_envs=4096, batch_size=4096, buffer_size=1 << 20)}
+
+
+def run(name, fused, iters, warmup):
+    from grasp_lab_salp_amd.sac import SAC
+    from grasp_lab_salp_amd.vec_env import SalpVecEnv
+    c = CONFIGS[name]
+    n = c["n_envs"]
+    env = SalpVecEnv(n, seed=0, infos=False)
+    model = SAC("MlpPolicy", env, learning_rate=3e-4, buffer_size=c["buffer_size"], learning_starts=n,
+                batch_size=c["batch_size"], tau=0.005, gamma=0.99, train_freq=1, gradient_steps=1, seed=0,
+                fused=fused)
+    model.learn((warmup + 1) * n, log_interval=warmup + 1)
+    for k in model.timing:
+        model.timing[k] = 0.0
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    model.learn(iters * n, log_interval=iters)
+    torch.cuda.synchronize()
+    el = time.perf_counter() - t0
+    out = {"fused": fused, "env_steps_per_s": iters * n / el, "iteration_ms": el / iters * 1e3,
+           "phase_ms": {k[:-2]: v / iters * 1e3 for k, v in model.timing.items()},
+           "losses": {k: model.logger[k] for k in ("critic_loss", "actor_loss", "ent_coef_loss", "ent_coef")},
+           "diverged_envs": model.nonfinite_resets}
+    env.close()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=300)
+    ap.add_argument("--warmup", type=int, default=30)
+    ap.add_argument("--configs", default="ref,wide")
+    a = ap.parse_args()
+    torch.cuda.set_device(0)
+    res = {"metric": "SAC env-steps/sec (collect + sample + update)", "unit": "env-steps/s", "iters": a.iters,
+           "warmup": a.warmup, "configs": {}}
+    for name in a.configs.split(","):
+        rows = [run(name, fused, a.iters, a.warmup) for fused in (True, False)]
+        res["configs"][name] = {**CONFIGS[name], "runs": rows,
+                                "fused_over_plain": rows[0]["env_steps_per_s"] / rows[1]["env_steps_per_s"]}
+    print(json.dumps(res), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -13,8 +13,9 @@ import subprocess, sys, os
 sys.path.insert(0, os.getcwd())
 from grasp_lab_salp_amd import build as B
 d, out = sys.argv[1], sys.argv[2]
-srcs = [os.path.join(d, "grasp_lab_salp_amd", "csrc", f) for f in ("salp_kernels.hip", "salp_gae.hip", "salp_ppo.hip",
-        "salp_ppo_mlp.hip", "salp_sort.hip", "salp_lstm.hip")]
+# the sources of today's build that the revision already had
+srcs = [os.path.join(d, "grasp_lab_salp_amd", "csrc", os.path.basename(f)) for f in B.SRCS]
+srcs = [s for s in srcs if os.path.exists(s)]
 subprocess.run([B.HIPCC, *B.FLAGS, "-o", out, *srcs], check=True)
 print(out)
 PY

@@ -196,6 +196,26 @@ static void abi_host_paths(void) {
         ad.obs_dim = 99;
         CHECK(salp_ppo_mlp_apply(&ad, NULL) == SALP_EINVAL);
     }
+    {   /* SAC: argument checks (no GPU) */
+        SalpReplay rb;
+        memset(&rb, 0, sizeof rb);
+        CHECK(salp_replay_add(&rb, NULL, NULL) == SALP_EINVAL);
+        rb.capacity = 4;
+        rb.n_envs = 3;
+        rb.obs_dim = 99;
+        CHECK(salp_replay_sample(&rb, NULL, NULL) == SALP_EINVAL);
+        CHECK(salp_sac_actor_head_forward(0, NULL, NULL, NULL, NULL, NULL, NULL) == SALP_EINVAL);
+        CHECK(salp_sac_actor_head_backward(4, NULL, NULL, NULL, NULL, NULL, NULL, NULL, NULL) == SALP_EINVAL);
+        SalpSacTd td;
+        memset(&td, 0, sizeof td);
+        td.batch = 4;
+        CHECK(salp_sac_td_head(&td, NULL) == SALP_EINVAL && salp_sac_td_head(NULL, NULL) == SALP_EINVAL);
+        SalpSacPi pi;
+        memset(&pi, 0, sizeof pi);
+        pi.batch = 4;
+        CHECK(salp_sac_pi_head(&pi, NULL) == SALP_EINVAL);
+        CHECK(salp_sac_polyak(0, NULL, NULL, 0.005, NULL) == SALP_EINVAL);
+    }
 }
 
 #ifdef SALP_SAN_GPU

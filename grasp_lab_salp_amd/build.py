@@ -21,9 +21,10 @@ FLAGS = ["-O3", "-std=c++17", f"--offload-arch={ARCH}", "-ffp-contract=off", "-f
 
 
 def deps():
+    """The sources, their headers and this file (FLAGS / FILE_FLAGS are part of the build)."""
     c = os.path.join(HERE, "csrc")
     return SRCS + [os.path.join(c, f) for f in os.listdir(c) if f.endswith(".h")] + [
-        os.path.join(HERE, "..", "include", "salp.h")]
+        os.path.join(HERE, "..", "include", "salp.h"), os.path.abspath(__file__)]
 
 
 def up_to_date():

@@ -679,8 +679,12 @@ __device__ __forceinline__ void rollout_boundary(Hot& h, ST S, const Params& P, 
 
 // All launch arguments in one struct: the env-step epilogue re-reads them from
 // the kernarg segment (scalar loads) where it runs, so that nothing it needs
-// is held in SGPRs across the tick loop — which then compiles exactly like a
-// standalone tick loop (its fp64 constants pinned in VGPRs, pin_params).
+// is held in SGPRs across the chunk's ticks.  That alone did not make
+// k_rollout's tick loops compile like a standalone tick loop (they shared a
+// register allocation with the inlined boundary: 804 instructions per full
+// tick against k_tick_bench's 675), so the re-seating k_rollout runs them in
+// a function of their own (wave_ticks below), which reads the arguments the
+// same way from the kernarg address it is given.
 struct RolloutArgs {
     double* S;
     Params P;
@@ -697,14 +701,18 @@ struct RolloutArgs {
 };
 static_assert(sizeof(RolloutArgs) % 8 == 0, "RolloutArgs is copied as 8-byte words");
 typedef const __attribute__((address_space(4))) uint64_t* KernargWords;
-__device__ __forceinline__ RolloutArgs fresh_args() {
-    KernargWords p = (KernargWords)__builtin_amdgcn_kernarg_segment_ptr();
+__device__ __forceinline__ RolloutArgs args_at(KernargWords p) {
     asm volatile("" : "+s"(p));   // opaque: the loads below stay where they are used
     uint64_t w[sizeof(RolloutArgs) / 8];
     for (size_t k = 0; k < sizeof(RolloutArgs) / 8; ++k) w[k] = p[k];
     RolloutArgs a;
     __builtin_memcpy(&a, w, sizeof a);
     return a;
+}
+// Kernels only: in a device function the kernarg segment pointer is null (the
+// call ABI does not pass it); a callee takes the address as an argument.
+__device__ __forceinline__ RolloutArgs fresh_args() {
+    return args_at((KernargWords)__builtin_amdgcn_kernarg_segment_ptr());
 }
 
 // Env-step boundaries park the whole wave's tick state in LDS (SpillSlot),
@@ -828,6 +836,79 @@ struct RollProf {
 };
 
 #if SALP_ROLLOUT_RESEAT
+// One chunk's ticks of a wave, as a separate (non-inlined) function: the three
+// tick loops get a register allocation of their own instead of sharing one
+// with the ~9 000 instructions of the inlined env-step boundary and the
+// re-seat (which cost the full-tick loop 130 instructions of constant
+// rebuilds, AGPR parking and SGPR-spill lane moves: profiles/r7_experiments.md).
+// The lane's Hot travels through its LDS slot (unspilled here, spilled back at
+// the end: the kernel holds no Hot between chunks); the two LDS columns are
+// passed as LDS pointers, so the slot and the float32 geometry cache are still
+// read with ds_read; the kernarg address is an argument (in a device function
+// the kernarg-segment builtin is null), made wave-uniform again so that the
+// launch arguments are scalar loads: read once at the top (chunk and steady_q8
+// stay in two SGPRs, the tick's constants are pinned in VGPRs) and P once more
+// after the loops for the flags, so that no other argument is held across them.  Returns TK_*: does the lane still tick, and does
+// its next tick need the geometry.  Private memory holds the registers this
+// function saves for its caller, written and read once per call.
+typedef __attribute__((address_space(3))) double LdsDouble;
+enum { TK_TICKING = 1, TK_UNSTEADY = 2 };
+__device__ __forceinline__ RolloutArgs args_of(uint64_t kernarg) {
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)kernarg);
+    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(kernarg >> 32));
+    return args_at((KernargWords)(((uint64_t)hi << 32) | lo));
+}
+__device__ __forceinline__ uint32_t tick_flags(const Hot& h, const Params& P, bool active) {
+    return (uint32_t)((h.ct < h.b2 ? TK_TICKING : 0) | (unsteady(h, P, active) ? TK_UNSTEADY : 0));
+}
+#if SALP_ROLLOUT_PROF
+#define ROLL_PROF_PARAM , RollProf& prof
+#define ROLL_PROF_ARG , prof
+#else
+#define ROLL_PROF_PARAM
+#define ROLL_PROF_ARG
+#endif
+template <bool RAND>
+__device__ __noinline__ uint32_t wave_ticks(uint64_t kernarg, LdsDouble* spp, LdsDouble* c32p, int64_t i,
+                                            uint32_t active ROLL_PROF_PARAM) {
+#if !SALP_ROLLOUT_PROF
+    RollProf prof;
+#endif
+    const salp::SpillSlot sp{(double*)spp};
+    const salp::Cache32 c32{(double*)c32p};
+    const RolloutArgs A = args_of(kernarg);
+    const int32_t chunk = A.chunk, steady_q8 = A.steady_q8;
+    Hot h;
+    salp::unspill<RAND>(h, sp, A.P, (uint64_t)(A.P.env_offset + i));
+    if (!active) h.b2 = -INFINITY;   // a finished lane (or an empty slot) ticks no more
+    prof.lap(RP_RESEAT);
+    const Params PV = salp::pin_params(A.P);
+    int32_t k = 0;
+    for (; k < chunk; ++k) {
+        if (__all(!(h.ct < h.b2) || salp::next_tick_steady(h, PV))) break;
+        if (h.ct < h.b2) salp::tick<false, RAND, true>(h, PV, c32);
+    }
+    prof.lap(RP_FULL, k);
+    const int32_t ks = (int32_t)(((int64_t)(chunk - k) * steady_q8) >> 8);
+    // steady ticks until every ticking lane of the wave is settled, then
+    // settled ticks (salp_device.h tick; lanes whose cycle has ended idle)
+    int32_t j = 0;
+    while (j < ks) {
+        bool settled = true;
+        if (h.ct < h.b2) settled = salp::tick<false, RAND, true, true>(h, PV, c32);
+        ++j;
+        if (__all(settled)) break;
+    }
+    prof.lap(RP_STEADY, j);
+    const int32_t j0 = j;
+    for (; j < ks; ++j)
+        if (h.ct < h.b2) salp::tick<false, RAND, true, true, true>(h, PV, c32);
+    prof.lap(RP_SETTLED, j - j0);
+    const uint32_t tk = tick_flags(h, args_of(kernarg).P, active != 0);   // re-read: only P, only here
+    salp::spill<RAND>(h, sp);
+    return tk;
+}
+
 template <bool RAND, bool POL>
 __global__ __launch_bounds__(kBlock) void k_rollout(RolloutArgs A) {
     double* const S = A.S;
@@ -845,17 +926,22 @@ __global__ __launch_bounds__(kBlock) void k_rollout(RolloutArgs A) {
     int64_t i = base + s;
     bool pending = false, active = false;
     int64_t steps = 0;
-    Hot h{};
-    if (i < P.n) {
-        pending = !A.fresh && SF(SALP_F_PENDING) != 0.0;
-        steps = A.B.steps_done ? A.B.steps_done[i] : 0;
-        active = !(A.max_steps > 0 && steps >= A.max_steps);
-        salp::load_hot<RAND>(h, S, P, i);
-        salp::resume_cycle(h, S, P, i);
-        salp::fill_cache32(P, h.c, salp::Cache32{s_cache32 + s});
+    uint32_t tk;                                     // TK_* of the env in slot s
+    {
+        Hot h{};
+        if (i < P.n) {
+            pending = !A.fresh && SF(SALP_F_PENDING) != 0.0;
+            steps = A.B.steps_done ? A.B.steps_done[i] : 0;
+            active = !(A.max_steps > 0 && steps >= A.max_steps);
+            salp::load_hot<RAND>(h, S, P, i);
+            salp::resume_cycle(h, S, P, i);
+            salp::fill_cache32(P, h.c, salp::Cache32{s_cache32 + s});
+        }
+        // slots past the end of the batch hold no env: never active, never stored
+        if (!active) h.b2 = -INFINITY;
+        tk = tick_flags(h, P, active);
+        salp::spill<RAND>(h, salp::SpillSlot{s_spill + s});   // from here on the slot holds the lane's Hot
     }
-    // slots past the end of the batch hold no env: never active, never stored
-    if (!active) h.b2 = -INFINITY;
     bool all_done = false;   // no env of the workgroup has an env-step left (max_steps)
     RollProf prof;
     prof.start();
@@ -863,9 +949,8 @@ __global__ __launch_bounds__(kBlock) void k_rollout(RolloutArgs A) {
         const bool last = c == A.n_chunks || all_done;
         const salp::SpillSlot sp{s_spill + s};
         // Env-step boundary of the lanes whose cycle ended (or that start one)
-        const bool need = active && (!pending || !(h.ct < h.b2));
-        bool uns = unsteady(h, P, active);
-        salp::spill<RAND>(h, sp);
+        const bool need = active && (!pending || !(tk & TK_TICKING));
+        bool uns = (tk & TK_UNSTEADY) != 0;
         if (need) {
             if (RAND) {
                 uns = lane_boundary_call<RAND, POL>(&A, s_spill + s, i, &pending, &active, &steps, s_cache32 + s);
@@ -876,6 +961,7 @@ __global__ __launch_bounds__(kBlock) void k_rollout(RolloutArgs A) {
         }
         if (last) {
             const RolloutArgs a = fresh_args();
+            Hot h;
             salp::unspill<RAND>(h, sp, a.P, (uint64_t)(a.P.env_offset + i));
             if (i < a.P.n) salp::store_hot<RAND>(h, a.S, a.P, i);
             break;
@@ -920,38 +1006,10 @@ __global__ __launch_bounds__(kBlock) void k_rollout(RolloutArgs A) {
         pending = (fl & 1) != 0;
         active = (fl & 2) != 0;
         steps = s_steps[s];
-        {
-            const RolloutArgs a = fresh_args();
-            salp::unspill<RAND>(h, salp::SpillSlot{s_spill + s}, a.P, (uint64_t)(a.P.env_offset + i));
-        }
-        if (!active) h.b2 = -INFINITY;   // a finished lane (or an empty slot) ticks no more
-        if (all_done) continue;          // next pass stores the state and leaves
-        prof.lap(RP_RESEAT);
-        const salp::Cache32 c32{s_cache32 + s};
-        const Params PV = salp::pin_params(P);
-        int32_t k = 0;
-        for (; k < A.chunk; ++k) {
-            if (__all(!(h.ct < h.b2) || salp::next_tick_steady(h, PV))) break;
-            if (h.ct < h.b2) salp::tick<false, RAND, true>(h, PV, c32);
-        }
-        prof.lap(RP_FULL, k);
-        const int32_t ks = (int32_t)(((int64_t)(A.chunk - k) * A.steady_q8) >> 8);
-        // steady ticks until every ticking lane of the wave is settled, then
-        // settled ticks (salp_device.h tick; lanes whose cycle has ended idle)
-        int32_t j = 0;
-        for (; j < ks; ++j) {
-            bool settled = true;
-            if (h.ct < h.b2) settled = salp::tick<false, RAND, true, true>(h, PV, c32);
-            if (__all(settled)) {
-                ++j;
-                break;
-            }
-        }
-        prof.lap(RP_STEADY, j);
-        const int32_t j0 = j;
-        for (; j < ks; ++j)
-            if (h.ct < h.b2) salp::tick<false, RAND, true, true, true>(h, PV, c32);
-        prof.lap(RP_SETTLED, j - j0);
+        if (all_done) continue;          // no lane is active: the next pass stores the state and leaves
+        // the chunk's ticks on the env now in slot s (wave_ticks: Hot from the slot and back)
+        tk = wave_ticks<RAND>((uint64_t)__builtin_amdgcn_kernarg_segment_ptr(), (LdsDouble*)(s_spill + s),
+                              (LdsDouble*)(s_cache32 + s), i, active ? 1u : 0u ROLL_PROF_ARG);
     }
     prof.flush();
     if (A.B.steps_done && i < P.n) A.B.steps_done[i] = steps;

@@ -179,6 +179,24 @@ def kernel_sha(lib_path, contains):
     return None
 
 
+def private_segment_size(lib_path, contains):
+    """Bytes of private (scratch) memory per lane of the one kernel whose
+    mangled name contains `contains`, or None (absent or ambiguous): the
+    `private_segment_fixed_size` field of its descriptor, the 32-bit word at
+    byte 4.  It covers the kernel's own spills and stack and those of the
+    device functions it calls."""
+    blob = open(lib_path, "rb").read()
+    for _ident, co in _code_objects(blob):
+        syms = _symbols(co)
+        hits = [n for n in syms if contains in n and n + ".kd" in syms]
+        if len(hits) == 1:
+            off, size = syms[hits[0] + ".kd"]
+            if size != 64:
+                return None
+            return struct.unpack_from("<I", co, off + 4)[0]
+    return None
+
+
 # The bench's dominant kernel: k_rollout<RAND = false, POL = false>.
 ROLLOUT_KERNEL = "k_rolloutILb0ELb0EE"
 # The PPO leg's collection kernel (config 5, 32 768 envs): the auto choice's

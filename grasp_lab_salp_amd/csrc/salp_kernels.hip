@@ -781,7 +781,9 @@ __device__ __forceinline__ bool unsteady(const Hot& h, const Params& P, bool act
 // register allocation of round 5's build stored two LDS addresses in place of
 // the discharge coefficient's slot (tests/test_gpu_collect.py, rand case;
 // tools/debug_collect_rand.py); the call keeps the boundary's registers apart
-// from the tick loop's.  The plain kernels keep it inline (the bench path).
+// from the tick loop's.  The plain kernels keep it inline (the bench path):
+// called, even without register saves, it spills more and the launch is 2.4 %
+// slower (profiles/r8_experiments.md, r8-3).
 template <bool RAND, bool POL>
 __device__ __forceinline__ bool lane_boundary(const RolloutArgs& a, salp::SpillSlot sp, int64_t i, bool& pending,
                                               bool& active, int64_t& steps, double* c32p) {
@@ -849,8 +851,21 @@ struct RollProf {
 // launch arguments are scalar loads: read once at the top (chunk and steady_q8
 // stay in two SGPRs, the tick's constants are pinned in VGPRs) and P once more
 // after the loops for the flags, so that no other argument is held across them.  Returns TK_*: does the lane still tick, and does
-// its next tick need the geometry.  Private memory holds the registers this
-// function saves for its caller, written and read once per call.
+// its next tick need the geometry.
+//
+// The call costs no register saves, and [[clang::not_tail_called]] is what
+// keeps it so.  wave_ticks has local linkage, does not recurse and its address
+// is never taken, so with interprocedural register allocation (on for AMDGPU)
+// LLVM saves no callee-saved register in it and gives each caller the exact
+// set it clobbers; the caller keeps its few live values (slot, env index,
+// flags, step count) in registers the callee leaves alone.  LLVM withdraws
+// that as soon as one call site of the function carries the IR `tail` marker
+// (TargetFrameLowering::isSafeForNoCSROpt).  Without the attribute the call in
+// k_rollout<false, true> got the marker, and wave_ticks<false> stored 132
+// registers to private memory in its prologue and loaded them back in its
+// epilogue for both plain kernels: 264 scratch instructions per call, ~8.6 GB
+// of HBM traffic per bench launch (profiles/r8_experiments.md).  The attribute
+// makes every call site ineligible for the marker; it changes nothing else.
 typedef __attribute__((address_space(3))) double LdsDouble;
 enum { TK_TICKING = 1, TK_UNSTEADY = 2 };
 __device__ __forceinline__ RolloutArgs args_of(uint64_t kernarg) {
@@ -869,8 +884,9 @@ __device__ __forceinline__ uint32_t tick_flags(const Hot& h, const Params& P, bo
 #define ROLL_PROF_ARG
 #endif
 template <bool RAND>
-__device__ __noinline__ uint32_t wave_ticks(uint64_t kernarg, LdsDouble* spp, LdsDouble* c32p, int64_t i,
-                                            uint32_t active ROLL_PROF_PARAM) {
+[[clang::not_tail_called]] __device__ __noinline__ uint32_t wave_ticks(uint64_t kernarg, LdsDouble* spp,
+                                                                       LdsDouble* c32p, int64_t i,
+                                                                       uint32_t active ROLL_PROF_PARAM) {
 #if !SALP_ROLLOUT_PROF
     RollProf prof;
 #endif

@@ -1079,9 +1079,11 @@ SD void set_coefficients(Hot& h, ST S, const Params& P, int64_t i) {
     h.rnd.amt0 = k.amt[0]; h.rnd.amt1 = k.amt[1]; h.rnd.amt2 = k.amt[2];
 }
 
+/* dir: the nozzle direction of (a1, a2) where the caller has computed it
+ * already (apply_step), else null */
 template <bool RAND = false, class ST>
 SD void set_control(Hot& h, ST S, const Params& P, int64_t i, double contraction, double coast,
-                    double a1, double a2, bool c32) {
+                    double a1, double a2, bool c32, const double* dir = nullptr) {
     set_coefficients<RAND>(h, S, P, i);
     SF(SALP_F_AVGV0) = 0.0; SF(SALP_F_AVGV1) = 0.0; SF(SALP_F_AVGV2) = 0.0;
     SF(SALP_F_AVGW0) = 0.0; SF(SALP_F_AVGW1) = 0.0; SF(SALP_F_AVGW2) = 0.0;
@@ -1089,7 +1091,11 @@ SD void set_control(Hot& h, ST S, const Params& P, int64_t i, double contraction
     h.coast = coast;
     h.c32 = c32;
     h.turn = nozzle_set_angles(S, P, i, a1, a2);
-    nozzle_direction(a1, a2, &h.d0);
+    if (dir) {
+        h.d0 = dir[0]; h.d1 = dir[1]; h.d2 = dir[2];
+    } else {
+        nozzle_direction(a1, a2, &h.d0);
+    }
     SF(SALP_F_CYCLE) = SF(SALP_F_CYCLE) + 1.0;
     h.ct = 0.0;
     const double sq = c32 ? (double)sqf((float)h.c) : h.c * h.c;
@@ -1117,6 +1123,46 @@ SD void cycle_prologue(const Hot& h, ST S, const Params& P, int64_t i) {
 }
 
 /* ------------------------------------------------ env-step prologue */
+/* The plain env-step prologue (no action randomisation) in two parts.
+ * plan_step: what follows from the action alone, without reading the env:
+ * the IK of the rescaled yaw, the nozzle direction of the new angles and the
+ * float32 geometry cache of the contraction.  apply_step: the rest, on the
+ * env's state, in begin_step's order on the same operands, so that
+ * apply_step(plan_step(...)) computes begin_step<false>'s bits.  k_rollout
+ * runs the plan of the next env-step on other lanes while the env's own lane
+ * finishes the previous one; begin_step itself (below) keeps its one-piece
+ * form for the kernels that run it in one lane, whose machine code (and with
+ * it their stamped PMC summaries) stays what it was. */
+struct StepPlan {
+    float a0, a1, a2;   /* the action */
+    double an1, an2;    /* nozzle_ik of the rescaled yaw */
+    double d[3];        /* nozzle_direction(an1, an2) */
+};
+SD StepPlan plan_step(const Params& P, float a0, float a1, float a2, Cache32 c32) {
+    StepPlan p;
+    p.a0 = a0; p.a1 = a1; p.a2 = a2;
+    const float r0 = a0 * 0.06f, r2 = a2 * (float)(PI / 2);
+    nozzle_ik((double)r2, true, &p.an1, &p.an2);
+    nozzle_direction(p.an1, p.an2, p.d);
+    fill_cache32(P, (double)r0, c32);
+    return p;
+}
+template <class ST>
+SD void apply_step(Hot& h, ST S, const Params& P, int64_t i, const StepPlan& p) {
+    SF(SALP_F_ACT0) = p.a0; SF(SALP_F_ACT1) = p.a1; SF(SALP_F_ACT2) = p.a2;
+    /* _rescale_action in float32 (src/salp_robot_env.py:166-174) */
+    const float r0 = p.a0 * 0.06f, r1 = p.a1 * 10.0f, r2 = p.a2 * (float)(PI / 2);
+    /* nozzle_solve with the planned angles */
+    SF(SALP_F_PREV_YAW) = SF(SALP_F_YAW);
+    SF(SALP_F_YAW) = (double)r2;
+    SF(SALP_F_PREV_ANGLE1) = SF(SALP_F_ANGLE1);
+    SF(SALP_F_PREV_ANGLE2) = SF(SALP_F_ANGLE2);
+    SF(SALP_F_ANGLE1) = p.an1;
+    SF(SALP_F_ANGLE2) = p.an2;
+    set_control<false>(h, S, P, i, (double)r0, (double)r1, p.an1, p.an2, true, p.d);
+    cycle_prologue(h, S, P, i);
+}
+
 /* SalpRobotEnv.step up to step_through_cycle's loop (src/salp_robot_env.py:
  * 196-210): float32 action rescale, IK, set_control, cycle prologue. */
 template <bool RAND = false, class ST>
@@ -1508,6 +1554,7 @@ SD void store_cold(const ColdRegs<RAND>& C, double* S, const Params& P, int64_t 
  * reload); RAND kernels park Hot::Rnd in those slots instead and recompute
  * the geometry on reload. */
 constexpr int SPILL_N = 63;
+constexpr int SPILL_D0 = 43;   /* cells of h.d0, h.d1, h.d2 (spill's order below) */
 struct SpillSlot {
     double* p;
     int stride = LANES;

@@ -781,9 +781,10 @@ __device__ __forceinline__ bool unsteady(const Hot& h, const Params& P, bool act
 // register allocation of round 5's build stored two LDS addresses in place of
 // the discharge coefficient's slot (tests/test_gpu_collect.py, rand case;
 // tools/debug_collect_rand.py); the call keeps the boundary's registers apart
-// from the tick loop's.  The plain kernels keep it inline (the bench path):
-// called, even without register saves, it spills more and the launch is 2.4 %
-// slower (profiles/r8_experiments.md, r8-3).
+// from the tick loop's.  k_rollout<false, true> (salp_collect without
+// randomisation) keeps it inline: called, even without register saves, it
+// spills more (profiles/r8_experiments.md, r8-3).  The plain rollout
+// (k_rollout<false, false>, the bench path) runs role_boundary instead.
 template <bool RAND, bool POL>
 __device__ __forceinline__ bool lane_boundary(const RolloutArgs& a, salp::SpillSlot sp, int64_t i, bool& pending,
                                               bool& active, int64_t& steps, double* c32p) {
@@ -808,11 +809,15 @@ __device__ __noinline__ bool lane_boundary_call(const RolloutArgs* a, double* sp
 // per wave, s_memtime cycles and loop iterations of each part of k_rollout's
 // chunk loop, summed over the launch's waves into g_roll_prof (read back by
 // salp_debug_rollout_prof): boundary + re-seat, full ticks, steady ticks,
-// settled ticks.
+// settled ticks; and, of the two-role boundary (role_boundary), the finish
+// lanes' loads, their finish part, the plan lanes' plan, and the join (apply,
+// stores, spill).  RP_BOUNDARY keeps what is left of the boundary (publishing,
+// numbering the jobs).
 #ifndef SALP_ROLLOUT_PROF
 #define SALP_ROLLOUT_PROF 0
 #endif
-enum { RP_BOUNDARY, RP_FULL, RP_STEADY, RP_SETTLED, RP_BARRIER, RP_RESEAT, RP_N };
+enum { RP_BOUNDARY, RP_FULL, RP_STEADY, RP_SETTLED, RP_BARRIER, RP_RESEAT, RP_B_LOAD, RP_B_FINISH, RP_B_PLAN,
+       RP_B_JOIN, RP_N };
 __device__ unsigned long long g_roll_prof[2][RP_N];   // [cycles | iterations][part]
 struct RollProf {
     unsigned long long cyc[RP_N] = {}, its[RP_N] = {};
@@ -925,12 +930,233 @@ template <bool RAND>
     return tk;
 }
 
+// The env-step boundary of k_rollout<false, false> in two roles.  Inlined per
+// lane (lane_boundary), the boundary ran in all four waves at about 8 lanes
+// in 64, epilogue and prologue one after the other.  Here the workgroup's
+// boundary envs ("jobs": the set bits of the 256-bit need mask, in lane
+// order) are packed onto lanes: lane j < 128 finishes job j's env-step
+// (cold loads, finish_step, buffer rows, reset, obs_before: rollout_boundary's
+// first half), while lane 128 + j plans the env's next one from (seed, env id,
+// step count) alone: sp_action, salp::plan_step with the float32 geometry
+// cache written straight into the slot's column.  After a barrier the finish
+// lane applies the plan (salp::apply_step), stores the cold block and spills
+// the slot.  More than 128 jobs (a launch's first boundary) take two passes.
+// Zero-tick cycles chain as in rollout_boundary, at most four rounds per env:
+// a job whose new cycle has already ended stays on its finish lane for another
+// round, and the round count comes from LDS, so every wave executes the same
+// barriers.  Per-env results are rollout_boundary's.
+enum { FL_PENDING = 1, FL_ACTIVE = 2, FL_TICKING = 4 };   // s_flags, per slot
+constexpr int kRoleJobs = kBlock / 2;
+struct RoleLds {
+    double* spill;            // s_spill
+    double* cache32;          // s_cache32
+    int64_t* steps;           // s_steps, per slot
+    uint8_t* flags;           // s_flags, per slot
+    const int16_t* slot_of;   // s_slot[b]: the slot each lane holds
+    uint64_t* mask;           // s_mask[b]: unsteady, by lane; the boundary envs' bits are set here
+    uint64_t* amask;          // s_amask[b]: active, by lane; cleared here when max_steps ends an env
+};
+
+// First half of one round of a job: rollout_boundary's `fin` part and the
+// observation its `beg` part stores.  Returns whether the env begins a step.
+template <class ST>
+__device__ __forceinline__ bool role_finish(Hot& h, ST S, const Params& P, int64_t i, bool& pending, bool& active,
+                                            int64_t& steps, int64_t max_steps, const SalpRolloutBuffers& B,
+                                            double* reward_sum, float* o, bool& have_o) {
+    const bool fin = active && pending && !(h.ct < h.b2);
+    if (fin) {
+        SF(SALP_F_STEP_COUNT) = SF(SALP_F_STEP_COUNT) + 1.0;
+        salp::StepOut r = salp::finish_step<false>(h, S, P, i, o, nullptr);
+        const bool reset = r.terminated || r.truncated;
+        if (B.capacity > 0) {
+            const size_t slot = (size_t)(steps % B.capacity);
+            const size_t row = slot * (size_t)P.n + (size_t)i;
+            if (B.obs)
+                for (int k = 0; k < P.obs_dim; ++k) B.obs[row * P.obs_dim + k] = o[k];
+            if (B.actions) {
+                B.actions[row * 3 + 0] = (float)SF(SALP_F_ACT0);
+                B.actions[row * 3 + 1] = (float)SF(SALP_F_ACT1);
+                B.actions[row * 3 + 2] = (float)SF(SALP_F_ACT2);
+            }
+            if (B.rewards) B.rewards[row] = (float)r.reward;
+            if (B.dones) B.dones[row] = (uint8_t)((r.terminated ? 1 : 0) | (r.truncated ? 2 : 0));
+        }
+        if (reward_sum) reward_sum[i] += r.reward;
+        ++steps;
+        pending = false;
+        if (reset) salp::reset_env_philox(h, S, P, i, B.obs_before ? o : nullptr);
+        have_o = true;
+        if (max_steps > 0 && steps >= max_steps) active = false;
+    }
+    const bool beg = active && !pending;
+    if (beg && B.obs_before) {
+        if (!have_o) {
+            const salp::Rot Rt = salp::rot_zyx(h.e0, h.e1, h.e2);
+            salp::observation(h, Rt, S, P, i, o);
+            have_o = true;
+        }
+        if (B.capacity > 0) {
+            const size_t row = (size_t)(steps % B.capacity) * (size_t)P.n + (size_t)i;
+            for (int k = 0; k < P.obs_dim; ++k) B.obs_before[row * P.obs_dim + k] = o[k];
+        }
+    }
+    return beg;
+}
+
+__device__ __forceinline__ uint64_t pack_floats(float lo, float hi) {
+    return (uint64_t)__float_as_uint(lo) | ((uint64_t)__float_as_uint(hi) << 32);
+}
+
+// Every lane of the workgroup calls this once per chunk, after it has written
+// its slot's s_flags / s_steps / s_slot[b] entries and its wave's s_mask[b]
+// (unsteady lanes that need no boundary) and s_amask[b] words.  On return (a
+// workgroup barrier is the last thing it does) the slots, flags, step counts
+// and both masks are what the re-seat reads.
+__device__ __forceinline__ void role_boundary(const RoleLds L, const int b, const int lane, const int64_t base,
+                                              const bool need, RollProf& prof) {
+    __shared__ uint64_t s_need[2][kBlock / 64];   // need ballots per wave (double-buffered like s_mask)
+    __shared__ uint32_t s_again[2][2][4];         // [b][pass][round]: some job of the pass takes another round
+    // Per job: the plan (two words of packed action floats, an1, an2; the
+    // direction goes to the slot's own d cells), then, from the finish lane to
+    // the plan lane of the next round: the step count to plan for, and whether to.
+    __shared__ uint64_t s_plan[4][kRoleJobs];
+    const uint64_t nb = __ballot(need);
+    if ((lane & 63) == 0) s_need[b][lane >> 6] = nb;
+    if (lane < 8) (&s_again[b][0][0])[lane] = 0u;
+    prof.lap(RP_BOUNDARY);
+    __syncthreads();
+    prof.lap(RP_BARRIER);
+    uint64_t nm[kBlock / 64];
+    int n_jobs = 0;
+#pragma unroll
+    for (int w = 0; w < kBlock / 64; ++w) {
+        nm[w] = s_need[b][w];
+        n_jobs += __popcll(nm[w]);
+    }
+    const bool fin_role = lane < kRoleJobs;
+    const int jr = lane & (kRoleJobs - 1);
+    for (int p = 0; p * kRoleJobs < n_jobs; ++p) {
+        const int j = p * kRoleJobs + jr;
+        const bool has = j < n_jobs;
+        int jl = 0, js = 0;
+        if (has) {
+            jl = nth_set_lane(nm, j);    // the lane that holds the job's env
+            js = L.slot_of[jl];          // its slot
+        }
+        const int64_t i = base + js;
+        const salp::SpillSlot sp{L.spill + js};
+        // finish lane: the env, in registers for all the job's rounds
+        salp::ColdRegs<false> C;
+        Hot hb;
+        float o[SALP_OBS_DIM_MAX];
+        bool have_o = false, pending = false, active = false, live = fin_role && has;
+        int64_t steps = 0;
+        // plan lane: whether the job's env begins a step this round, and its step count then
+        bool go = false;
+        double sc = 0.0;
+        prof.lap(RP_BOUNDARY);
+        if (has) {
+            const RolloutArgs a = fresh_args();
+            const int fl = L.flags[js];
+            if (fin_role) {
+                salp::load_cold<false>(C, a.S, a.P, i);
+                salp::unspill<false>(hb, sp, a.P, (uint64_t)(a.P.env_offset + i));
+                pending = (fl & FL_PENDING) != 0;
+                active = (fl & FL_ACTIVE) != 0;
+                steps = L.steps[js];
+            } else {
+                const bool fin = (fl & FL_ACTIVE) && (fl & FL_PENDING) && !(fl & FL_TICKING);
+                const int64_t st = L.steps[js] + (fin ? 1 : 0);
+                go = !(fin && a.max_steps > 0 && st >= a.max_steps);   // else max_steps ends the env: no plan
+                sc = salp::sref((const double*)a.S, a.P, i, SALP_F_STEP_COUNT) + (fin ? 1.0 : 0.0);
+            }
+        }
+        prof.lap(RP_B_LOAD);
+        for (int r = 0;; ++r) {
+            bool beg = false;
+            if (fin_role) {
+                if (live) {
+                    const RolloutArgs a = fresh_args();
+                    beg = role_finish(hb, &C, a.P, i, pending, active, steps, a.max_steps, a.B, a.reward_sum, o,
+                                      have_o);
+                }
+                prof.lap(RP_B_FINISH);
+            } else {
+                if (go) {
+                    const RolloutArgs a = fresh_args();
+                    float act[3];
+                    sp_action(a.P.seed, (uint64_t)(a.P.env_offset + i), (uint64_t)sc, act);
+                    const salp::StepPlan pl =
+                        salp::plan_step(a.P, act[0], act[1], act[2], salp::Cache32{L.cache32 + js});
+                    s_plan[0][jr] = pack_floats(pl.a0, pl.a1);
+                    s_plan[1][jr] = pack_floats(pl.a2, 0.0f);
+                    s_plan[2][jr] = (uint64_t)__double_as_longlong(pl.an1);
+                    s_plan[3][jr] = (uint64_t)__double_as_longlong(pl.an2);
+                    // The finish lane holds the slot's Hot in registers and takes d
+                    // from these cells before it spills; what its unspill read from
+                    // them is overwritten on every path that reaches here.
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) sp[salp::SPILL_D0 + k] = pl.d[k];
+                }
+                prof.lap(RP_B_PLAN);
+            }
+            prof.lap(RP_BOUNDARY);
+            __syncthreads();
+            prof.lap(RP_BARRIER);
+            if (live) {
+                const RolloutArgs a = fresh_args();
+                if (beg) {
+                    salp::StepPlan pl;
+                    const uint64_t w0 = s_plan[0][jr], w1 = s_plan[1][jr];
+                    pl.a0 = __uint_as_float((uint32_t)w0);
+                    pl.a1 = __uint_as_float((uint32_t)(w0 >> 32));
+                    pl.a2 = __uint_as_float((uint32_t)w1);
+                    pl.an1 = __longlong_as_double((long long)s_plan[2][jr]);
+                    pl.an2 = __longlong_as_double((long long)s_plan[3][jr]);
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) pl.d[k] = sp[salp::SPILL_D0 + k];
+                    salp::apply_step(hb, &C, a.P, i, pl);
+                    pending = true;
+                }
+                // a zero-tick cycle has ended already: its env-step finishes in the next round
+                const bool again = r < 3 && active && pending && !(hb.ct < hb.b2);
+                if (again) {
+                    s_again[b][p][r] = 1u;
+                    s_plan[0][jr] =
+                        (uint64_t)__double_as_longlong(salp::sref(&C, a.P, i, SALP_F_STEP_COUNT) + 1.0);
+                    s_plan[1][jr] = (a.max_steps > 0 && steps + 1 >= a.max_steps) ? 0u : 1u;
+                } else {
+                    s_plan[1][jr] = 0u;
+                    salp::store_cold<false>(C, a.S, a.P, i);
+                    salp::spill<false>(hb, sp);
+                    L.flags[js] = (uint8_t)((pending ? FL_PENDING : 0) | (active ? FL_ACTIVE : 0));
+                    L.steps[js] = steps;
+                    const uint64_t bit = 1ull << (jl & 63);
+                    if (unsteady(hb, a.P, active)) atomicOr((unsigned long long*)&L.mask[jl >> 6], bit);
+                    if (!active) atomicAnd((unsigned long long*)&L.amask[jl >> 6], ~bit);
+                    live = false;
+                }
+            }
+            prof.lap(RP_B_JOIN);
+            __syncthreads();
+            prof.lap(RP_BARRIER);
+            if (r == 3 || !s_again[b][p][r]) break;
+            go = false;
+            if (!fin_role && has && s_plan[1][jr] != 0u) {
+                go = true;
+                sc = __longlong_as_double((long long)s_plan[0][jr]);
+            }
+        }
+    }
+}
+
 template <bool RAND, bool POL>
 __global__ __launch_bounds__(kBlock) void k_rollout(RolloutArgs A) {
     double* const S = A.S;
     const Params& P = A.P;
     const int64_t base = (int64_t)blockIdx.x * blockDim.x;
     const int lane = (int)threadIdx.x;
+    constexpr bool kRoles = !RAND && !POL;   // the plain rollout: two-role boundary (role_boundary)
     __shared__ double s_cache32[salp::C32_N * salp::LANES];
     __shared__ double s_spill[salp::SPILL_N * salp::LANES];
     __shared__ int64_t s_steps[kBlock];
@@ -967,7 +1193,24 @@ __global__ __launch_bounds__(kBlock) void k_rollout(RolloutArgs A) {
         // Env-step boundary of the lanes whose cycle ended (or that start one)
         const bool need = active && (!pending || !(tk & TK_TICKING));
         bool uns = (tk & TK_UNSTEADY) != 0;
-        if (need) {
+        if constexpr (kRoles) {
+            const int b = (int)(c & 1);
+            // publish the slot, then the two-role boundary (role_boundary), whose
+            // last barrier is the re-seat's
+            s_steps[s] = steps;
+            s_flags[s] = (uint8_t)((pending ? FL_PENDING : 0) | (active ? FL_ACTIVE : 0) |
+                                   ((tk & TK_TICKING) ? FL_TICKING : 0));
+            s_slot[b][lane] = (int16_t)s;
+            const uint64_t ballot = __ballot(uns && !need);
+            const uint64_t aballot = __ballot(active);
+            if ((lane & 63) == 0) {
+                s_mask[b][lane >> 6] = ballot;
+                s_amask[b][lane >> 6] = aballot;
+            }
+            role_boundary(RoleLds{s_spill, s_cache32, s_steps, s_flags, s_slot[b], s_mask[b], s_amask[b]}, b, lane,
+                          base, need, prof);
+            if (last) steps = s_steps[s];
+        } else if (need) {
             if (RAND) {
                 uns = lane_boundary_call<RAND, POL>(&A, s_spill + s, i, &pending, &active, &steps, s_cache32 + s);
             } else {
@@ -983,21 +1226,24 @@ __global__ __launch_bounds__(kBlock) void k_rollout(RolloutArgs A) {
             break;
         }
         // Re-seat: lane k of the workgroup takes the k-th env in the order
-        // (unsteady envs by lane, then steady envs by lane).  One barrier; the
-        // double buffers keep the next boundary's writes off this one's reads.
+        // (unsteady envs by lane, then steady envs by lane).  One barrier
+        // (role_boundary's last one in the plain rollout); the double buffers
+        // keep the next boundary's writes off this one's reads.
         const int b = (int)(c & 1);
-        s_steps[s] = steps;
-        s_flags[s] = (uint8_t)((pending ? 1 : 0) | (active ? 2 : 0));
-        s_slot[b][lane] = (int16_t)s;
-        const uint64_t ballot = __ballot(uns);
-        const uint64_t aballot = __ballot(active);
-        if ((lane & 63) == 0) {
-            s_mask[b][lane >> 6] = ballot;
-            s_amask[b][lane >> 6] = aballot;
+        if constexpr (!kRoles) {
+            s_steps[s] = steps;
+            s_flags[s] = (uint8_t)((pending ? 1 : 0) | (active ? 2 : 0));
+            s_slot[b][lane] = (int16_t)s;
+            const uint64_t ballot = __ballot(uns);
+            const uint64_t aballot = __ballot(active);
+            if ((lane & 63) == 0) {
+                s_mask[b][lane >> 6] = ballot;
+                s_amask[b][lane >> 6] = aballot;
+            }
+            prof.lap(RP_BOUNDARY);
+            __syncthreads();
+            prof.lap(RP_BARRIER);
         }
-        prof.lap(RP_BOUNDARY);
-        __syncthreads();
-        prof.lap(RP_BARRIER);
         uint64_t m[kBlock / 64];
         int n_uns = 0;
         uint64_t any_active = 0;

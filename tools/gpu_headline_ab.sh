@@ -7,8 +7,9 @@ mkdir -p gpurun_out
 OUT=${OUT:-gpurun_out/headline_ab.txt}
 for r in $(seq ${ROUNDS:-2}); do
     for lib in ${LIBS:-product}; do
-        l=$lib; [ "$lib" = product ] && l=""
-        v=$(SALP_AB_OLD_ABI=1 SALP_LIB=$l timeout -k 10 300 python bench.py --no-cpu-baseline --no-lockstep --no-parity-check --no-ppo \
+        # the in-tree build loads as usual; SALP_AB_OLD_ABI is refused without another library
+        e="SALP_AB_OLD_ABI=1 SALP_LIB=$lib"; [ "$lib" = product ] && e="SALP_LIB="
+        v=$(env $e timeout -k 10 300 python bench.py --no-cpu-baseline --no-lockstep --no-parity-check --no-ppo \
             2>/dev/null | grep '^{' | python -c "import json,sys; d=json.load(sys.stdin); print(round(d['value']/1e6,2), round(d['kernel_ms_per_launch'],3))") || exit 1
         echo "$lib $v" >> "$OUT"
     done

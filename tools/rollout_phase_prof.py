@@ -21,7 +21,10 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 from grasp_lab_salp_amd import _lib  # noqa: E402
 from grasp_lab_salp_amd.batched_env import BatchedSalpEnv  # noqa: E402
 
-PARTS = ["boundary", "full", "steady", "settled", "barrier", "reseat"]
+# the last four: inside k_rollout<false, false>'s two-role boundary (finish
+# lanes: cold loads + unspill, the finish part; plan lanes: the plan; finish
+# lanes again: apply + stores + spill); "boundary" is the rest of it
+PARTS = ["boundary", "full", "steady", "settled", "barrier", "reseat", "b_load", "b_finish", "b_plan", "b_join"]
 
 
 def main():

@@ -192,6 +192,49 @@ class SalpSacPi(ctypes.Structure):
     ]
 
 
+SAC_HIDDEN = 256          # include/salp.h SALP_SAC_HIDDEN
+SAC_NET_IN_MAX = 17       # include/salp.h SALP_SAC_NET_IN_MAX
+SAC_NET_OUT_MAX = 6       # include/salp.h SALP_SAC_NET_OUT_MAX
+SAC_NET_MAX_NETS = 4      # include/salp.h SALP_SAC_NET_MAX_NETS
+SAC_NET_N_TENSORS = 6     # include/salp.h SALP_SAC_NET_N_TENSORS
+_P4 = ctypes.c_void_p * SAC_NET_MAX_NETS
+
+
+class SalpSacNetForward(ctypes.Structure):
+    _fields_ = [
+        ("batch", ctypes.c_int64),
+        ("d0", ctypes.c_int32),
+        ("d1", ctypes.c_int32),
+        ("out_dim", ctypes.c_int32),
+        ("n_nets", ctypes.c_int32),
+        ("params", _P4),
+        ("x0", _P4),
+        ("x1", _P4),
+        ("out", _P4),
+        ("h1", _P4),
+        ("h2", _P4),
+    ]
+
+
+class SalpSacNetBackward(ctypes.Structure):
+    _fields_ = [
+        ("batch", ctypes.c_int64),
+        ("d0", ctypes.c_int32),
+        ("d1", ctypes.c_int32),
+        ("out_dim", ctypes.c_int32),
+        ("n_nets", ctypes.c_int32),
+        ("params", _P4),
+        ("x0", _P4),
+        ("x1", _P4),
+        ("h1", _P4),
+        ("h2", _P4),
+        ("dout", _P4),
+        ("dparams", _P4),
+        ("dx1", ctypes.c_void_p),
+        ("workspace", ctypes.c_void_p),
+    ]
+
+
 class SalpTraceBuffer(ctypes.Structure):
     _fields_ = [
         ("max_samples", ctypes.c_int64),
@@ -257,6 +300,13 @@ SIGNATURES = {
     "salp_sac_td_head": (ctypes.c_int, [ctypes.POINTER(SalpSacTd), _V]),
     "salp_sac_pi_head": (ctypes.c_int, [ctypes.POINTER(SalpSacPi), _V]),
     "salp_sac_polyak": (ctypes.c_int, [ctypes.c_int64, _V, _V, ctypes.c_double, _V]),
+    "salp_sac_net_num_params": (ctypes.c_int64, [ctypes.c_int, ctypes.c_int]),
+    "salp_sac_net_offset": (ctypes.c_int64, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "salp_sac_net_tile_rows": (ctypes.c_int, []),
+    "salp_sac_net_max_blocks": (ctypes.c_int, []),
+    "salp_sac_net_workspace_floats": (ctypes.c_int64, [ctypes.c_int64] + [ctypes.c_int] * 4),
+    "salp_sac_net_forward": (ctypes.c_int, [ctypes.POINTER(SalpSacNetForward), _V]),
+    "salp_sac_net_backward": (ctypes.c_int, [ctypes.POINTER(SalpSacNetBackward), _V]),
 }
 
 

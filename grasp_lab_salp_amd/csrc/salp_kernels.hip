@@ -2552,6 +2552,15 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t salp_sac_pi_launch(c
 extern "C" __attribute__((visibility("hidden"))) hipError_t salp_sac_polyak_launch(int64_t n, const float* params,
                                                                                     float* target, double tau,
                                                                                     void* stream);
+extern "C" __attribute__((visibility("hidden"))) int salp_sac_net_tile_rows_impl(void);
+extern "C" __attribute__((visibility("hidden"))) int salp_sac_net_max_blocks_impl(void);
+extern "C" __attribute__((visibility("hidden"))) int64_t salp_sac_net_offset_impl(int in, int od, int tensor);
+extern "C" __attribute__((visibility("hidden"))) int64_t salp_sac_net_workspace_impl(int64_t B, int d0, int d1, int od,
+                                                                                     int n_nets);
+extern "C" __attribute__((visibility("hidden"))) hipError_t salp_sac_net_fwd_launch(const SalpSacNetForward* f,
+                                                                                     void* stream);
+extern "C" __attribute__((visibility("hidden"))) hipError_t salp_sac_net_bwd_launch(const SalpSacNetBackward* b,
+                                                                                     void* stream);
 
 extern "C" {
 
@@ -3127,6 +3136,75 @@ int salp_sac_polyak(int64_t n, const float* params, float* target, double tau, v
     if (n <= 0 || !params || !target) return fail(nullptr, SALP_EINVAL, "salp_sac_polyak: bad argument");
     if (!(tau >= 0 && tau <= 1)) return fail(nullptr, SALP_EINVAL, "salp_sac_polyak: tau must be in [0, 1]");
     return check_hip(nullptr, salp_sac_polyak_launch(n, params, target, tau, stream), "k_polyak");
+}
+
+namespace {
+bool sac_net_dims_ok(int in, int od) {
+    return in >= 1 && in <= SALP_SAC_NET_IN_MAX && od >= 1 && od <= SALP_SAC_NET_OUT_MAX;
+}
+// the part SalpSacNetForward and SalpSacNetBackward share; nullptr if it is sound, else what is wrong
+const char* sac_net_bad(int64_t batch, int d0, int d1, int od, int n_nets, const float* const* params,
+                        const float* const* x0, const float* const* x1) {
+    if (batch <= 0 || batch > INT32_MAX) return "batch must be in 1 .. 2^31 - 1";
+    if (d0 < 1 || d1 < 0 || !sac_net_dims_ok(d0 + d1, od)) return "d0 >= 1, d1 >= 0, d0 + d1 <= 17 and out_dim in 1 .. 6";
+    if (n_nets < 1 || n_nets > SALP_SAC_NET_MAX_NETS) return "n_nets must be in 1 .. 4";
+    for (int i = 0; i < n_nets; ++i)
+        if (!params[i] || !x0[i] || (d1 > 0 && !x1[i])) return "null params, x0 or x1";
+    return nullptr;
+}
+}  // namespace
+
+int64_t salp_sac_net_num_params(int in_dim, int out_dim) {
+    return salp_sac_net_offset(in_dim, out_dim, SALP_SAC_NET_N_TENSORS);
+}
+
+int64_t salp_sac_net_offset(int in_dim, int out_dim, int tensor) {
+    if (!sac_net_dims_ok(in_dim, out_dim) || tensor < 0 || tensor > SALP_SAC_NET_N_TENSORS) {
+        fail(nullptr, SALP_EINVAL, "salp_sac_net_offset: in_dim in 1 .. 17, out_dim in 1 .. 6, tensor in 0 .. 6");
+        return -1;
+    }
+    return salp_sac_net_offset_impl(in_dim, out_dim, tensor);
+}
+
+int salp_sac_net_tile_rows(void) { return salp_sac_net_tile_rows_impl(); }
+int salp_sac_net_max_blocks(void) { return salp_sac_net_max_blocks_impl(); }
+
+int64_t salp_sac_net_workspace_floats(int64_t batch, int d0, int d1, int out_dim, int n_nets) {
+    if (batch <= 0 || batch > INT32_MAX || d0 < 1 || d1 < 0 || !sac_net_dims_ok(d0 + d1, out_dim) || n_nets < 1 ||
+        n_nets > SALP_SAC_NET_MAX_NETS) {
+        fail(nullptr, SALP_EINVAL, "salp_sac_net_workspace_floats: bad argument");
+        return -1;
+    }
+    return salp_sac_net_workspace_impl(batch, d0, d1, out_dim, n_nets);
+}
+
+int salp_sac_net_forward(const SalpSacNetForward* f, void* stream) {
+    if (!f) return fail(nullptr, SALP_EINVAL, "salp_sac_net_forward: null argument");
+    if (const char* bad = sac_net_bad(f->batch, f->d0, f->d1, f->out_dim, f->n_nets, f->params, f->x0, f->x1))
+        return fail(nullptr, SALP_EINVAL, std::string("salp_sac_net_forward: ") + bad);
+    for (int i = 0; i < f->n_nets; ++i) {
+        if (!f->out[i]) return fail(nullptr, SALP_EINVAL, "salp_sac_net_forward: null out");
+        if (!f->h1[i] != !f->h2[i])
+            return fail(nullptr, SALP_EINVAL, "salp_sac_net_forward: h1 and h2 are both NULL or both set");
+    }
+    return check_hip(nullptr, salp_sac_net_fwd_launch(f, stream), "k_sac_net_fwd");
+}
+
+int salp_sac_net_backward(const SalpSacNetBackward* b, void* stream) {
+    if (!b) return fail(nullptr, SALP_EINVAL, "salp_sac_net_backward: null argument");
+    if (const char* bad = sac_net_bad(b->batch, b->d0, b->d1, b->out_dim, b->n_nets, b->params, b->x0, b->x1))
+        return fail(nullptr, SALP_EINVAL, std::string("salp_sac_net_backward: ") + bad);
+    for (int i = 0; i < b->n_nets; ++i) {
+        if (!b->h1[i] || !b->h2[i] || !b->dout[i])
+            return fail(nullptr, SALP_EINVAL, "salp_sac_net_backward: null h1, h2 or dout");
+        if (!b->dparams[i] != !b->dparams[0])
+            return fail(nullptr, SALP_EINVAL, "salp_sac_net_backward: dparams are all NULL or all set");
+    }
+    if (!b->dparams[0] && !b->dx1)
+        return fail(nullptr, SALP_EINVAL, "salp_sac_net_backward: neither dparams nor dx1 is set");
+    if (b->dx1 && b->d1 == 0) return fail(nullptr, SALP_EINVAL, "salp_sac_net_backward: dx1 needs d1 > 0");
+    if (!b->workspace) return fail(nullptr, SALP_EINVAL, "salp_sac_net_backward: null workspace");
+    return check_hip(nullptr, salp_sac_net_bwd_launch(b, stream), "k_sac_net_bwd");
 }
 
 }  // extern "C"

@@ -32,6 +32,9 @@ launch over flat parameter buffers.  ``fused=False`` runs the same step from
 the plain torch expressions below (``torch_squashed_gaussian``,
 ``torch_td_head``, ``torch_pi_head``, index-op add / sample): the readable
 restatement, and the one that runs on the CPU.  Both draw the same batches.
+``fused_mlp=True`` (default off) replaces the library GEMMs too: the actor and
+the critics run as the kernels of csrc/salp_sac_mlp.hip (``fused_actor``,
+``fused_critic``), forward and backward, over the same ``nn.Module`` parameters.
 
 Collection is lock-step ``salp_step`` on a stream of its own, with the
 divergence guard, episode statistics and HIP-event phase timings of
@@ -54,6 +57,7 @@ from ._abi import INFO, INFO_DIM
 __all__ = ["SAC", "SACPolicy", "ReplayBuffer", "squashed_gaussian", "td_head", "pi_head", "polyak",
            "torch_squashed_gaussian", "torch_td_head", "torch_pi_head", "torch_polyak", "torch_replay_add",
            "torch_replay_indices", "scale_action", "unscale_action", "critic_phase", "actor_phase",
+           "fused_nets", "fused_actor", "fused_critic",
            "LOG_STD_MIN", "LOG_STD_MAX", "REPLAY_STREAM"]
 
 LOG_STD_MIN, LOG_STD_MAX = -20.0, 2.0     # SB3 sac/policies.py
@@ -273,6 +277,110 @@ def polyak(params_flat, target_flat, tau):
     return target_flat
 
 
+class _NetFn(torch.autograd.Function):
+    """One pass of up to four 256-256 ReLU networks of one shape through
+    salp_sac_net_forward / _backward (include/salp.h): a launch forward, the
+    row kernel and the reduction backward.  ``params``: every network's
+    tensors in the kernel's flat order, views into one buffer per network
+    (``_Actor.net_params``, ``_Critic.net_params``).  The activations are kept
+    only if ``keep`` (something asks for a gradient); the parameter gradients come back
+    as views of one flat gradient buffer per pass, and ``x1``'s (the action
+    columns) summed over the networks.  ``x0`` gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, x0, x1, n_nets, out_dim, keep, *params):
+        B, d0 = x0.shape
+        d1 = 0 if x1 is None else x1.shape[1]
+        per = len(params) // n_nets
+        dev = x0.device
+        outs = [torch.empty((B, out_dim), dtype=torch.float32, device=dev) for _ in range(n_nets)]
+        h = torch.empty((2, n_nets, B, _lib.SAC_HIDDEN), dtype=torch.float32, device=dev) if keep else None
+        f = _lib.SalpSacNetForward(batch=B, d0=d0, d1=d1, out_dim=out_dim, n_nets=n_nets)
+        for i in range(n_nets):
+            f.params[i] = params[i * per].data_ptr()
+            f.x0[i] = x0.data_ptr()
+            f.x1[i] = x1.data_ptr() if d1 else None
+            f.out[i] = outs[i].data_ptr()
+            if keep:
+                f.h1[i], f.h2[i] = h[0, i].data_ptr(), h[1, i].data_ptr()
+        _lib.check(_lib.load().salp_sac_net_forward(ctypes.byref(f), _stream(dev)))
+        if keep:
+            ctx.save_for_backward(x0, x1, h, *params)
+            ctx.dims = (n_nets, out_dim, per)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *douts):
+        x0, x1, h, *params = ctx.saved_tensors
+        n_nets, out_dim, per = ctx.dims
+        if ctx.needs_input_grad[0]:
+            raise RuntimeError("the fused networks give no gradient to their first input")
+        B, d0 = x0.shape
+        d1 = 0 if x1 is None else x1.shape[1]
+        dev = x0.device
+        want_x1 = ctx.needs_input_grad[1]
+        want_p = any(ctx.needs_input_grad[5:])
+        lib = _lib.load()
+        P = lib.salp_sac_net_num_params(d0 + d1, out_dim)
+        new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)  # noqa: E731
+        douts = [torch.zeros((B, out_dim), dtype=torch.float32, device=dev) if d is None else d.contiguous()
+                 for d in douts]
+        gflat = new(n_nets, P) if want_p else None
+        dx1 = new(B, d1) if want_x1 else None
+        ws = new(lib.salp_sac_net_workspace_floats(B, d0, d1, out_dim, n_nets))
+        b = _lib.SalpSacNetBackward(batch=B, d0=d0, d1=d1, out_dim=out_dim, n_nets=n_nets,
+                                    dx1=dx1.data_ptr() if want_x1 else None, workspace=ws.data_ptr())
+        for i in range(n_nets):
+            b.params[i] = params[i * per].data_ptr()
+            b.x0[i] = x0.data_ptr()
+            b.x1[i] = x1.data_ptr() if d1 else None
+            b.h1[i], b.h2[i] = h[0, i].data_ptr(), h[1, i].data_ptr()
+            b.dout[i] = douts[i].data_ptr()
+            b.dparams[i] = gflat[i].data_ptr() if want_p else None
+        _lib.check(lib.salp_sac_net_backward(ctypes.byref(b), _stream(dev)))
+        grads = [None] * len(params)
+        if want_p:
+            for i in range(n_nets):
+                off = 0
+                for k in range(per):
+                    p = params[i * per + k]
+                    grads[i * per + k] = gflat[i, off:off + p.numel()].view_as(p)
+                    off += p.numel()
+        return (None, dx1, None, None, None, *grads)
+
+
+def fused_nets(x0, x1, nets, out_dim):
+    """``nets`` (lists of parameter tensors in the kernel's flat order, each
+    list contiguous in one buffer) evaluated on ``concat(x0, x1)`` (``x1`` may
+    be None) in one launch: a tuple of [B, out_dim] outputs, differentiable
+    in the parameters and in ``x1``."""
+    B = x0.shape[0]
+    x0 = _f32("x0", x0, (B, x0.shape[1]))
+    if x1 is not None:
+        x1 = _f32("x1", x1, (B, x1.shape[1]))
+    params = [p for net in nets for p in net]
+    keep = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x0, x1, *params))
+    return _NetFn.apply(x0, x1, len(nets), out_dim, keep, *params)
+
+
+def fused_actor(actor, obs):
+    """``actor(obs)`` through the fused network: (mean, raw log-std)."""
+    out, = fused_nets(obs, None, [actor.net_params()], 2 * actor.mu.out_features)
+    k = actor.mu.out_features
+    return out[:, :k], out[:, k:]
+
+
+def fused_critic(critic, obs, action, detach=False):
+    """``critic(obs, action)`` through the fused network, both Q-networks in
+    one launch.  ``detach``: the parameters get no gradient (the backward then
+    computes the action's gradient alone)."""
+    nets = critic.net_params()
+    if detach:
+        nets = [[p.detach() for p in net] for net in nets]
+    q1, q2 = fused_nets(obs, action, nets, 1)
+    return q1.squeeze(-1), q2.squeeze(-1)
+
+
 # ------------------------------------------------------------- replay buffer
 class ReplayBuffer:
     """SB3 ``ReplayBuffer`` in device memory: rings [capacity, n_envs, ...]
@@ -374,17 +482,52 @@ def _mlp(d_in, hidden, d_out=None):
     return nn.Sequential(*layers)
 
 
+def _flatten(ps):
+    """Make the parameters views into one new flat buffer, back to back in the given order."""
+    flat = torch.cat([p.detach().reshape(-1) for p in ps])
+    off = 0
+    for p in ps:
+        p.data = flat[off:off + p.numel()].view_as(p)
+        off += p.numel()
+    return flat
+
+
+def _is_flat(flat, ps):
+    if flat is None:
+        return False
+    off = 0
+    for p in ps:
+        if p.data_ptr() != flat.data_ptr() + off * flat.element_size() or not p.is_contiguous():
+            return False
+        off += p.numel()
+    return off == flat.numel()
+
+
 class _Actor(nn.Module):
     def __init__(self, obs_dim, act_dim, hidden):
         super().__init__()
         self.latent_pi = _mlp(obs_dim, hidden)
         self.mu = nn.Linear(hidden[-1], act_dim)
         self.log_std = nn.Linear(hidden[-1], act_dim)
+        self.flat = None
 
     def forward(self, obs):
         """(mean, raw log-std); the heads clamp the log-std."""
         z = self.latent_pi(obs)
         return self.mu(z), self.log_std(z)
+
+    def net_params(self):
+        """The parameters in the fused network's flat order (include/salp.h
+        SalpSacNetTensor): the two heads are one 2 act_dim-row layer, mu's rows
+        first."""
+        return [*self.latent_pi.parameters(), self.mu.weight, self.log_std.weight, self.mu.bias, self.log_std.bias]
+
+    def flatten_(self):
+        self.flat = _flatten(self.net_params())
+        return self
+
+    def is_flat(self):
+        return _is_flat(self.flat, self.net_params())
 
 
 class _Critic(nn.Module):
@@ -401,25 +544,16 @@ class _Critic(nn.Module):
         x = torch.cat([obs, action], dim=1)
         return self.qf0(x).squeeze(-1), self.qf1(x).squeeze(-1)
 
+    def net_params(self):
+        """Each Q-network's parameters in the fused network's flat order (torch's own)."""
+        return [list(self.qf0.parameters()), list(self.qf1.parameters())]
+
     def flatten_(self):
-        ps = list(self.parameters())
-        flat = torch.cat([p.detach().reshape(-1) for p in ps])
-        off = 0
-        for p in ps:
-            p.data = flat[off:off + p.numel()].view_as(p)
-            off += p.numel()
-        self.flat = flat
+        self.flat = _flatten(list(self.parameters()))
         return self
 
     def is_flat(self):
-        if self.flat is None:
-            return False
-        off = 0
-        for p in self.parameters():
-            if p.data_ptr() != self.flat.data_ptr() + off * self.flat.element_size() or not p.is_contiguous():
-                return False
-            off += p.numel()
-        return off == self.flat.numel()
+        return _is_flat(self.flat, list(self.parameters()))
 
 
 class SACPolicy(nn.Module):
@@ -431,7 +565,7 @@ class SACPolicy(nn.Module):
 
     def __init__(self, obs_dim, act_dim=3, hidden=(256, 256), device=None):
         super().__init__()
-        self.obs_dim, self.act_dim = int(obs_dim), int(act_dim)
+        self.obs_dim, self.act_dim, self.hidden = int(obs_dim), int(act_dim), tuple(hidden)
         self.actor = _Actor(obs_dim, act_dim, hidden)
         self.critic = _Critic(obs_dim, act_dim, hidden)
         self.critic_target = copy.deepcopy(self.critic)
@@ -442,6 +576,7 @@ class SACPolicy(nn.Module):
         self.flatten_()
 
     def flatten_(self):
+        self.actor.flatten_()
         self.critic.flatten_()
         self.critic_target.flatten_()
         return self
@@ -455,20 +590,44 @@ class SACPolicy(nn.Module):
 
 
 # ------------------------------------------------------------- gradient step
-def critic_phase(policy, log_alpha, batch, eps_pi, eps_next, gamma, target_entropy, fused):
+def _check_fused_mlp(policy, fused, device):
+    """``fused_mlp=True`` needs the HIP heads, a GPU and the 256-256 networks in their flat buffers."""
+    if torch.device(device).type != "cuda":
+        raise ValueError("fused_mlp=True runs HIP kernels: it needs a ROCm GPU device")
+    if not fused:
+        raise ValueError("fused_mlp=True needs fused=True: the networks' kernels feed the fused heads")
+    if tuple(policy.hidden) != (_lib.SAC_HIDDEN, _lib.SAC_HIDDEN):
+        raise ValueError(f"fused_mlp=True is built for hidden sizes (256, 256), not {tuple(policy.hidden)}")
+    if policy.obs_dim + policy.act_dim > _lib.SAC_NET_IN_MAX or 2 * policy.act_dim > _lib.SAC_NET_OUT_MAX:
+        raise ValueError("fused_mlp=True: obs_dim + act_dim <= 17 and act_dim <= 3")
+    if not (policy.actor.is_flat() and policy.critic.is_flat() and policy.critic_target.is_flat()):
+        raise ValueError("fused_mlp=True: the networks' parameters must be views into their flat buffers: "
+                         "SACPolicy.flatten_()")
+
+
+def critic_phase(policy, log_alpha, batch, eps_pi, eps_next, gamma, target_entropy, fused, fused_mlp=False):
     """First half of SB3 ``SAC.train``'s gradient step, up to the backward of
     the critic and entropy-coefficient losses (no optimizer step).  The
     critics' gradients are added to their ``.grad`` as autograd does;
     ``log_alpha.grad`` is overwritten with this batch's gradient on both paths.  ``batch`` = (obs,
     actions, next_obs, rewards, dones); ``eps_*`` [B, 3] N(0, 1) noise for the
-    actions at obs and next_obs.  Returns what :func:`actor_phase` needs."""
+    actions at obs and next_obs.  ``fused_mlp``: the networks run as
+    :func:`fused_actor` / :func:`fused_critic` launches instead of torch
+    modules.  Returns what :func:`actor_phase` needs."""
     obs, act, next_obs, rew, done = batch
     head = squashed_gaussian if fused else torch_squashed_gaussian
-    a_pi, logp = head(*policy.actor(obs), eps_pi)
+    if fused_mlp:
+        _check_fused_mlp(policy, fused, obs.device)
+        actor, critic, critic_target = (lambda o: fused_actor(policy.actor, o),
+                                        lambda o, a: fused_critic(policy.critic, o, a),
+                                        lambda o, a: fused_critic(policy.critic_target, o, a))
+    else:
+        actor, critic, critic_target = policy.actor, policy.critic, policy.critic_target
+    a_pi, logp = head(*actor(obs), eps_pi)
     with torch.no_grad():
-        a_next, logp_next = head(*policy.actor(next_obs), eps_next)
-        q1t, q2t = policy.critic_target(next_obs, a_next)
-    q1, q2 = policy.critic(obs, act)
+        a_next, logp_next = head(*actor(next_obs), eps_next)
+        q1t, q2t = critic_target(next_obs, a_next)
+    q1, q2 = critic(obs, act)
     if fused:
         out, target, dq1, dq2, alpha = td_head(rew, done, q1t, q2t, logp_next, q1, q2, logp, log_alpha, gamma,
                                                target_entropy)
@@ -486,11 +645,16 @@ def critic_phase(policy, log_alpha, batch, eps_pi, eps_next, gamma, target_entro
             "critic_loss": critic_loss, "ent_coef_loss": ent_coef_loss}
 
 
-def actor_phase(policy, st, fused):
+def actor_phase(policy, st, fused, fused_mlp=False):
     """Second half: critics(obs, a_pi), the actor loss and its backward into
     the actor's parameters only (SB3 lets it reach the critics too and zeroes
-    those gradients before their next step).  Returns the actor loss."""
-    q1_pi, q2_pi = policy.critic(st["obs"], st["a_pi"])
+    those gradients before their next step; ``fused_mlp`` does not compute
+    them).  Returns the actor loss."""
+    if fused_mlp:
+        _check_fused_mlp(policy, fused, st["obs"].device)
+        q1_pi, q2_pi = fused_critic(policy.critic, st["obs"], st["a_pi"], detach=True)
+    else:
+        q1_pi, q2_pi = policy.critic(st["obs"], st["a_pi"])
     params = list(policy.actor.parameters())
     if fused:
         out, dlogp, dq1, dq2 = pi_head(st["alpha"], st["logp"], q1_pi, q2_pi)
@@ -512,7 +676,9 @@ class SAC:
     or ``(n, "step")``; ``gradient_steps=-1``: as many gradient steps as
     transitions collected.  ``ent_coef``: ``"auto"``, ``"auto_<init>"`` or a
     fixed value.  ``fused``: HIP kernels around the GEMMs (default on a GPU) or
-    plain torch.  ``tensorboard_log`` is accepted and unused (``history`` holds
+    plain torch.  ``fused_mlp`` (default off; needs ``fused``, a GPU and the
+    256-256 networks): the networks themselves run as the HIP kernels of
+    csrc/salp_sac_mlp.hip, forward and backward, in the collection too.  ``tensorboard_log`` is accepted and unused (``history`` holds
     the rows a logger would get); ``device`` other than ``None`` / ``"auto"``
     must be the simulator's device.  ``seed`` seeds the policy's init (without
     moving the process-wide generator), the exploration noise and the sampler.
@@ -520,7 +686,8 @@ class SAC:
 
     def __init__(self, policy, env, learning_rate=3e-4, buffer_size=1_000_000, learning_starts=100, batch_size=256,
                  tau=0.005, gamma=0.99, train_freq=1, gradient_steps=1, ent_coef="auto", target_entropy="auto",
-                 seed=0, fused=None, verbose=0, tensorboard_log=None, device="auto", reset_nonfinite=True):
+                 seed=0, fused=None, verbose=0, tensorboard_log=None, device="auto", reset_nonfinite=True,
+                 fused_mlp=False):
         if policy not in ("MlpPolicy", None) and not isinstance(policy, SACPolicy):
             raise ValueError("policy must be 'MlpPolicy' or a SACPolicy")
         self.env = env
@@ -554,6 +721,9 @@ class SAC:
                 self.policy = SACPolicy(self.obs_dim, self.act_dim, device=self.device)
         if self.fused and not (self.policy.critic.is_flat() and self.policy.critic_target.is_flat()):
             raise ValueError("the critics' parameters must be views into their flat buffers: SACPolicy.flatten_()")
+        self.fused_mlp = bool(fused_mlp)
+        if self.fused_mlp:
+            _check_fused_mlp(self.policy, self.fused, self.device)
         self.target_entropy = -float(self.act_dim) if target_entropy == "auto" else float(target_entropy)
         init, auto = 1.0, isinstance(ent_coef, str)
         if auto:
@@ -613,7 +783,8 @@ class SAC:
             return 2.0 * torch.rand((self.n_envs, 3), generator=self.sample_gen, device=self.device) - 1.0
         eps = torch.randn((self.n_envs, 3), generator=self.sample_gen, device=self.device)
         head = squashed_gaussian if self.fused else torch_squashed_gaussian
-        return head(*self.policy.actor(obs), eps)[0]
+        mu_ls = fused_actor(self.policy.actor, obs) if self.fused_mlp else self.policy.actor(obs)
+        return head(*mu_ls, eps)[0]
 
     def collect_step(self):
         """One lock-step env-step of every env into the replay buffer."""
@@ -659,11 +830,11 @@ class SAC:
         if self.ent_coef_opt is not None:
             self.ent_coef_opt.zero_grad(set_to_none=True)
         st = critic_phase(pol, self.log_ent_coef, batch, self._noise(), self._noise(), self.gamma,
-                          self.target_entropy, self.fused)
+                          self.target_entropy, self.fused, self.fused_mlp)
         self.critic_opt.step()
         if self.ent_coef_opt is not None:
             self.ent_coef_opt.step()
-        actor_loss = actor_phase(pol, st, self.fused)
+        actor_loss = actor_phase(pol, st, self.fused, self.fused_mlp)
         self.actor_opt.step()
         if self.fused:
             polyak(pol.critic.flat, pol.critic_target.flat, self.tau)

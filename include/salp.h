@@ -547,6 +547,91 @@ int salp_sac_pi_head(const SalpSacPi* p, void* stream);
  * then rounded to float32. */
 int salp_sac_polyak(int64_t n, const float* params, float* target, double tau, void* stream);
 
+/* SAC's networks (csrc/salp_sac_mlp.hip): one 3-layer float32 ReLU network
+ *   out = W3 relu(W2 relu(W1 x + b1) + b2) + b3,   in -> 256 -> 256 -> out,
+ * forward and backward, the 256 x 256 products on the f32-input matrix cores
+ * (exact f32).  It is the actor (in = obs_dim, out = 6: rows 0-2 of the head
+ * are mu, rows 3-5 the raw log-std) and each critic (in = obs_dim + 3, out =
+ * 1).  These entry points were added under ABI 14 without a new version
+ * number: nothing that existed changed, and a library of ABI 14 built before
+ * them is recognised by the missing symbol salp_sac_net_forward.
+ *
+ * A network's parameters are one flat float32 vector, the six tensors in
+ * torch Linear shapes ([out][in] row-major) back to back in SalpSacNetTensor
+ * order; gradients use the same layout.  1 <= in_dim <= SALP_SAC_NET_IN_MAX,
+ * 1 <= out_dim <= SALP_SAC_NET_OUT_MAX.  salp_sac_net_offset(in, out, t) is
+ * the offset of tensor t (t = SALP_SAC_NET_N_TENSORS: the total, which
+ * salp_sac_net_num_params returns too); -1 for a bad argument. */
+#define SALP_SAC_HIDDEN 256
+#define SALP_SAC_NET_IN_MAX 17
+#define SALP_SAC_NET_OUT_MAX 6
+#define SALP_SAC_NET_MAX_NETS 4
+typedef enum SalpSacNetTensor {
+    SALP_SAC_NET_W1 = 0,   /* [256][in] */
+    SALP_SAC_NET_B1,       /* [256] */
+    SALP_SAC_NET_W2,       /* [256][256] */
+    SALP_SAC_NET_B2,       /* [256] */
+    SALP_SAC_NET_W3,       /* [out][256] */
+    SALP_SAC_NET_B3,       /* [out] */
+    SALP_SAC_NET_N_TENSORS
+} SalpSacNetTensor;
+int64_t salp_sac_net_num_params(int in_dim, int out_dim);
+int64_t salp_sac_net_offset(int in_dim, int out_dim, int tensor);
+/* Rows per tile of the kernels, and the most row blocks the backward runs per
+ * network (a block takes tiles bx, bx + blocks, ...), so a batch of
+ * tile_rows * max_blocks + 1 is the smallest at which a block takes two tiles. */
+int salp_sac_net_tile_rows(void);
+int salp_sac_net_max_blocks(void);
+/* One launch evaluates n_nets <= 4 networks of the same shape on `batch` rows.
+ * Network i reads the row concat(x0[i][:, :d0], x1[i][:, :d1]) (in_dim = d0 +
+ * d1; d1 = 0: x1 unused), so critic(obs, action) needs no concatenation.
+ * out[i] [batch][out_dim].  h1[i], h2[i] [batch][256] receive the post-ReLU
+ * activations for the backward; both NULL: not kept (out has the same bits). */
+typedef struct SalpSacNetForward {
+    int64_t batch;
+    int32_t d0;
+    int32_t d1;
+    int32_t out_dim;
+    int32_t n_nets;
+    const float* params[4];
+    const float* x0[4];     /* [batch][d0] */
+    const float* x1[4];     /* [batch][d1] */
+    float* out[4];
+    float* h1[4];
+    float* h2[4];
+} SalpSacNetForward;
+int salp_sac_net_forward(const SalpSacNetForward* f, void* stream);
+/* The backward of the same launch from dout[i] [batch][out_dim] and the kept
+ * h1[i], h2[i]:  dz2 = (dout W3) (h2 > 0),  dz1 = (dz2 W2) (h1 > 0)  (zero
+ * gradient where the stored activation is exactly 0, torch's
+ * threshold_backward).  dparams[i] (all set or all NULL) receive the flat
+ * parameter gradient, overwritten: every row block accumulates its tiles in
+ * registers and writes one float32 partial, the partials are summed in fp64
+ * in a fixed order.  dx1 [batch][d1] (or NULL; needs d1 > 0) receives
+ * (dz1 W1)[:, d0:] summed over the networks in index order: the action's
+ * gradient through both critics.  At least one of the two is set.  No
+ * floating-point atomics: two calls give identical bits.  The workspace size
+ * takes the struct's own fields (d0 and d1 apart: the dx1 partials are
+ * [n_nets][batch][d1]); it is fully written before it is read. */
+typedef struct SalpSacNetBackward {
+    int64_t batch;
+    int32_t d0;
+    int32_t d1;
+    int32_t out_dim;
+    int32_t n_nets;
+    const float* params[4];
+    const float* x0[4];
+    const float* x1[4];
+    const float* h1[4];
+    const float* h2[4];
+    const float* dout[4];
+    float* dparams[4];
+    float* dx1;
+    float* workspace;       /* salp_sac_net_workspace_floats(batch, d0, d1, out_dim, n_nets) */
+} SalpSacNetBackward;
+int64_t salp_sac_net_workspace_floats(int64_t batch, int d0, int d1, int out_dim, int n_nets);
+int salp_sac_net_backward(const SalpSacNetBackward* b, void* stream);
+
 /* ------------------------------------------------ Robot / Nozzle level */
 /* The reference's Robot API for callers that drive the robot directly,
  * without the task env (src/compare_trajectories.py:120-168,

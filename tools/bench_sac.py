@@ -1,9 +1,10 @@
 """The on-device SAC learner (grasp_lab_salp_amd/sac.py), fused and plain.
 
-    python tools/bench_sac.py [--iters 300] [--warmup 30] [--configs ref,wide]
+    python tools/bench_sac.py [--iters 300] [--warmup 30] [--configs ref,wide] [--out FILE]
 
-Prints one JSON line.  Per configuration and for ``fused`` on and off: full
-iteration env-steps/s (collection + sample + update, host clock around a
+Prints one JSON line (and writes it to FILE).  Per configuration, for ``fused``
+on and off and for ``fused=True, fused_mlp=True`` (the networks as HIP kernels
+too, csrc/salp_sac_mlp.hip): full iteration env-steps/s (collection + sample + update, host clock around a
 device synchronise) and the milliseconds per iteration of each phase (HIP
 events: the collection, and the first gradient step's sample and update).
 
@@ -13,7 +14,7 @@ events: the collection, and the first gradient step's sample and update).
 
 learning_starts is one env-step, so every timed iteration trains; the warm-up
 iterations (untimed) fill the buffer and load the GEMMs' kernels.  The
-fused / plain ratio is reported, not judged.
+fused / plain and fused_mlp / fused ratios are reported, not judged.
 """
 import argparse
 import json
@@ -30,7 +31,7 @@ CONFIGS = {"ref": dict(n_envs=8, batch_size=256, buffer_size=100000),
            "wide": dict(n_envs=4096, batch_size=4096, buffer_size=1 << 20)}
 
 
-def run(name, fused, iters, warmup):
+def run(name, fused, iters, warmup, fused_mlp=False):
     from grasp_lab_salp_amd.sac import SAC
     from grasp_lab_salp_amd.vec_env import SalpVecEnv
     c = CONFIGS[name]
@@ -38,7 +39,7 @@ def run(name, fused, iters, warmup):
     env = SalpVecEnv(n, seed=0, infos=False)
     model = SAC("MlpPolicy", env, learning_rate=3e-4, buffer_size=c["buffer_size"], learning_starts=n,
                 batch_size=c["batch_size"], tau=0.005, gamma=0.99, train_freq=1, gradient_steps=1, seed=0,
-                fused=fused)
+                fused=fused, fused_mlp=fused_mlp)
     model.learn((warmup + 1) * n, log_interval=warmup + 1)
     for k in model.timing:
         model.timing[k] = 0.0
@@ -47,7 +48,7 @@ def run(name, fused, iters, warmup):
     model.learn(iters * n, log_interval=iters)
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
-    out = {"fused": fused, "env_steps_per_s": iters * n / el, "iteration_ms": el / iters * 1e3,
+    out = {"fused": fused, "fused_mlp": fused_mlp, "env_steps_per_s": iters * n / el, "iteration_ms": el / iters * 1e3,
            "phase_ms": {k[:-2]: v / iters * 1e3 for k, v in model.timing.items()},
            "losses": {k: model.logger[k] for k in ("critic_loss", "actor_loss", "ent_coef_loss", "ent_coef")},
            "diverged_envs": model.nonfinite_resets}
@@ -60,15 +61,21 @@ def main():
     ap.add_argument("--iters", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--configs", default="ref,wide")
+    ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     a = ap.parse_args()
     torch.cuda.set_device(0)
     res = {"metric": "SAC env-steps/sec (collect + sample + update)", "unit": "env-steps/s", "iters": a.iters,
            "warmup": a.warmup, "configs": {}}
     for name in a.configs.split(","):
-        rows = [run(name, fused, a.iters, a.warmup) for fused in (True, False)]
+        rows = [run(name, fused, a.iters, a.warmup, mlp) for fused, mlp in ((True, False), (False, False), (True, True))]
         res["configs"][name] = {**CONFIGS[name], "runs": rows,
-                                "fused_over_plain": rows[0]["env_steps_per_s"] / rows[1]["env_steps_per_s"]}
-    print(json.dumps(res), flush=True)
+                                "fused_over_plain": rows[0]["env_steps_per_s"] / rows[1]["env_steps_per_s"],
+                                "fused_mlp_over_fused": rows[2]["env_steps_per_s"] / rows[0]["env_steps_per_s"]}
+    line = json.dumps(res)
+    print(line, flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
 
 
 if __name__ == "__main__":

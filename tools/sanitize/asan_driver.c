@@ -215,6 +215,23 @@ static void abi_host_paths(void) {
         pi.batch = 4;
         CHECK(salp_sac_pi_head(&pi, NULL) == SALP_EINVAL);
         CHECK(salp_sac_polyak(0, NULL, NULL, 0.005, NULL) == SALP_EINVAL);
+        /* the fused networks: layout queries and the checks that come before any launch */
+        CHECK(salp_sac_net_num_params(17, 1) == 256 * 17 + 256 + 256 * 256 + 256 + 256 + 1);
+        CHECK(salp_sac_net_offset(9, 1, SALP_SAC_NET_N_TENSORS) == salp_sac_net_num_params(9, 1));
+        CHECK(salp_sac_net_num_params(18, 1) == -1 && salp_sac_net_offset(9, 7, 0) == -1);
+        CHECK(salp_sac_net_workspace_floats(64, 10, 3, 1, 5) == -1);
+        CHECK(salp_sac_net_workspace_floats(33, 10, 3, 1, 2) == 2 * 2 * salp_sac_net_num_params(13, 1) + 2 * 33 * 3);
+        SalpSacNetForward nf;
+        memset(&nf, 0, sizeof nf);
+        CHECK(salp_sac_net_forward(&nf, NULL) == SALP_EINVAL && salp_sac_net_forward(NULL, NULL) == SALP_EINVAL);
+        nf.batch = 4; nf.d0 = 10; nf.d1 = 3; nf.out_dim = 1; nf.n_nets = 5;
+        CHECK(salp_sac_net_forward(&nf, NULL) == SALP_EINVAL);
+        nf.n_nets = 2;
+        CHECK(salp_sac_net_forward(&nf, NULL) == SALP_EINVAL);   /* null params */
+        SalpSacNetBackward nbk;
+        memset(&nbk, 0, sizeof nbk);
+        nbk.batch = 4; nbk.d0 = 10; nbk.d1 = 3; nbk.out_dim = 1; nbk.n_nets = 2;
+        CHECK(salp_sac_net_backward(&nbk, NULL) == SALP_EINVAL && salp_sac_net_backward(NULL, NULL) == SALP_EINVAL);
     }
 }
 

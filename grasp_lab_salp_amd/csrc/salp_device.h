@@ -1124,13 +1124,14 @@ SD void cycle_prologue(const Hot& h, ST S, const Params& P, int64_t i) {
 
 /* ------------------------------------------------ env-step prologue */
 /* The plain env-step prologue (no action randomisation) in two parts.
- * plan_step: what follows from the action alone, without reading the env:
- * the IK of the rescaled yaw, the nozzle direction of the new angles and the
- * float32 geometry cache of the contraction.  apply_step: the rest, on the
- * env's state, in begin_step's order on the same operands, so that
- * apply_step(plan_step(...)) computes begin_step<false>'s bits.  k_rollout
- * runs the plan of the next env-step on other lanes while the env's own lane
- * finishes the previous one; begin_step itself (below) keeps its one-piece
+ * plan_angles, plan_direction and plan_cache: what follows from the action
+ * alone, without reading the env: the IK of the rescaled yaw, the nozzle
+ * direction of the new angles, and the float32 geometry cache of the
+ * contraction (k_rollout runs the cache on another wave than the angles).
+ * apply_step: the rest, on the env's state, in begin_step's order on the same
+ * operands, so that apply_step on such a plan computes begin_step<false>'s
+ * bits.  k_rollout runs the plan of the next env-step on other lanes while
+ * the env's own lane finishes the previous one; begin_step itself (below) keeps its one-piece
  * form for the kernels that run it in one lane, whose machine code (and with
  * it their stamped PMC summaries) stays what it was. */
 struct StepPlan {
@@ -1138,14 +1139,15 @@ struct StepPlan {
     double an1, an2;    /* nozzle_ik of the rescaled yaw */
     double d[3];        /* nozzle_direction(an1, an2) */
 };
-SD StepPlan plan_step(const Params& P, float a0, float a1, float a2, Cache32 c32) {
-    StepPlan p;
-    p.a0 = a0; p.a1 = a1; p.a2 = a2;
-    const float r0 = a0 * 0.06f, r2 = a2 * (float)(PI / 2);
+SD void plan_angles(StepPlan& p) {
+    const float r2 = p.a2 * (float)(PI / 2);
     nozzle_ik((double)r2, true, &p.an1, &p.an2);
-    nozzle_direction(p.an1, p.an2, p.d);
+}
+SD void plan_direction(StepPlan& p) { nozzle_direction(p.an1, p.an2, p.d); }
+/* the float32 geometry cache of the planned contraction (begin_step's fill_cache32) */
+SD void plan_cache(const Params& P, float a0, Cache32 c32) {
+    const float r0 = a0 * 0.06f;
     fill_cache32(P, (double)r0, c32);
-    return p;
 }
 template <class ST>
 SD void apply_step(Hot& h, ST S, const Params& P, int64_t i, const StepPlan& p) {
@@ -1389,6 +1391,92 @@ SD StepOut finish_step(Hot& h, ST S, const Params& P, int64_t i, float* obs,
     return out;
 }
 
+/* finish_step<false> without its observation (and without info): the same
+ * operations on the same operands in the same order for everything else.
+ * k_rollout<false, false> computes the observation of the ended step on
+ * another wave from the same state (finish_step leaves what observation reads
+ * alone); finish_step itself keeps its one-piece body for every other kernel. */
+template <class ST>
+SD StepOut finish_core(Hot& h, ST S, const Params& P, int64_t i) {
+    StepOut out;
+    const Rot R = rot_zyx(h.e0, h.e1, h.e2);
+    double vw[3];
+    world_frame(h.e0, h.e1, h.e2, h.v0, h.v1, h.v2, vw, sm_poly());
+    const double px = h.p0, py = h.p1;
+    double path = SF(SALP_F_PATH_LEN) + np_norm2(px - SF(SALP_F_LAST_PX), py - SF(SALP_F_LAST_PY));
+    SF(SALP_F_PATH_LEN) = path;
+    SF(SALP_F_LAST_PX) = px; SF(SALP_F_LAST_PY) = py;
+    double svel = SF(SALP_F_SUM_VEL) + np_norm2(vw[0], vw[1]);
+    SF(SALP_F_SUM_VEL) = svel;
+    const double tx = SF(SALP_F_TARGET0), ty = SF(SALP_F_TARGET1);
+    const double dx = px - tx, dy = py - ty;
+    const double dist = np_norm2(dx, dy);
+    double comp[7];
+    comp[0] = (-dist + SF(SALP_F_PREV_DIST)) * 100;
+    SF(SALP_F_PREV_DIST) = dist;
+    double b0, b1;
+    rot_body_xy(R, dx, dy, &b0, &b1);
+    comp[1] = -0.5 * fabs(sm_atan2(-b1, -b0));
+    const float a2 = (float)SF(SALP_F_ACT2);
+    const double ep_len = SF(SALP_F_EP_LEN);
+    if (ep_len == 0.0) {
+        double ch = (double)a2 - SF(SALP_F_PREV_A2);
+        comp[2] = -1.0 * (ch * ch);
+    } else {
+        float ch = a2 - (float)SF(SALP_F_PREV_A2);
+        comp[2] = (double)(-(ch * ch));
+    }
+    comp[3] = -10.0 * fabs(SF(SALP_F_AVGW2));
+    comp[4] = -0.1;
+    comp[5] = -100.0 * fabs(SF(SALP_F_AVGV1));
+    comp[6] = 0.0;
+    const int nob = (int)SF(SALP_F_N_OBST);
+    double md = 0.0;
+#pragma unroll
+    for (int k = 0; k < SALP_MAX_OBSTACLES; ++k) {
+        if (k >= nob) break;
+        double d = np_norm2(px - SF(SALP_F_OBST0 + 2 * k), py - SF(SALP_F_OBST0 + 2 * k + 1));
+        if (k == 0 || d < md) md = d;
+    }
+    if (nob > 0) {
+        double danger = 2.0 * P.obstacle_radius;
+        if (md < danger) comp[6] = -1.0 * (1.0 - md / danger);
+    }
+    double reward = comp[0] + comp[1] + comp[2] + comp[3] + comp[4] + comp[5] + comp[6];
+    bool l32;
+    double Lc, Wc;
+    body_lw(P, h.phase, h.ct, h.refill, h.mx, h.c, h.cr, h.rr, h.c32, &Lc, &Wc, &l32);
+    double thr = l32 ? (double)((float)P.obstacle_radius + (float)Lc / 2.0f)
+                     : P.obstacle_radius + Lc / 2;
+    bool hit = false;
+#pragma unroll
+    for (int k = 0; k < SALP_MAX_OBSTACLES; ++k) {
+        if (k >= nob) break;
+        double d = np_norm2(px - SF(SALP_F_OBST0 + 2 * k), py - SF(SALP_F_OBST0 + 2 * k + 1));
+        if (d < thr) hit = true;
+    }
+    bool done = false, trunc = false;
+    if (dist < 0.2) { done = true; reward += 500.0; }
+    else if (dist > 5.0) { trunc = true; reward -= 200.0; }
+    if (hit) { trunc = true; reward -= 200.0; }
+    if (SF(SALP_F_CYCLE) >= (double)P.max_cycles) { trunc = true; reward -= 50.0; }
+    SF(SALP_F_EP_LEN) = ep_len + 1.0;
+    SF(SALP_F_EP_RETURN) = SF(SALP_F_EP_RETURN) + reward;
+    const double sa0 = SF(SALP_F_SUM_A0) + (double)(float)SF(SALP_F_ACT0);
+    const double sa1 = SF(SALP_F_SUM_A1) + (double)(float)SF(SALP_F_ACT1);
+    const double sa2 = SF(SALP_F_SUM_ABS_A2) + (double)fabsf(a2);
+    SF(SALP_F_SUM_A0) = sa0; SF(SALP_F_SUM_A1) = sa1; SF(SALP_F_SUM_ABS_A2) = sa2;
+#pragma unroll
+    for (int k = 0; k < 7; ++k) SF(SALP_F_SUM_R0 + k) = SF(SALP_F_SUM_R0 + k) + comp[k];
+    SF(SALP_F_PREV_A2) = (double)a2;
+    SF(SALP_F_PENDING) = 0.0;
+    out.reward = reward;
+    out.terminated = done;
+    out.truncated = trunc;
+    out.hit = hit;
+    return out;
+}
+
 /* ---------------------------------------------------------- reset */
 /* Philox draws replacing np.random in generate_target_point("random") and
  * _generate_obstacles (src/salp_robot_env.py:449-559). */
@@ -1494,6 +1582,27 @@ SD void reset_env(Hot& h, ST S, const Params& P, int64_t i, const float* tgt,
     }
 }
 
+/* The observation reset_env returns, from the draw alone: robot_reset leaves
+ * the body at the origin, at rest and level, and reset_env stores the target
+ * and the obstacles as given here, so salp::observation runs on the same
+ * operands.  k_rollout computes it on another wave than the reset. */
+SD void reset_observation(const Params& P, const float* tgt, const float* obst, int nob, float* obs) {
+    Hot h;
+    h.p0 = h.p1 = 0.0; h.v0 = h.v1 = 0.0; h.w2 = 0.0;
+    ColdRegs<false> C;
+    ColdRegs<false>* S = &C;
+    const int64_t i = 0;
+    SF(SALP_F_TARGET0) = tgt[0]; SF(SALP_F_TARGET1) = tgt[1];
+#pragma unroll
+    for (int k = 0; k < SALP_MAX_OBSTACLES; ++k) {
+        SF(SALP_F_OBST0 + 2 * k) = k < nob ? (double)obst[2 * k] : 0.0;
+        SF(SALP_F_OBST0 + 2 * k + 1) = k < nob ? (double)obst[2 * k + 1] : 0.0;
+    }
+    SF(SALP_F_N_OBST) = nob;
+    const Rot R = rot_zyx(0.0, 0.0, 0.0);
+    observation(h, R, S, P, i, obs);
+}
+
 template <class ST>
 SD void reset_env_philox(Hot& h, ST S, const Params& P, int64_t i, float* obs) {
     float tgt[2], obst[2 * SALP_MAX_OBSTACLES];
@@ -1555,6 +1664,7 @@ SD void store_cold(const ColdRegs<RAND>& C, double* S, const Params& P, int64_t 
  * the geometry on reload. */
 constexpr int SPILL_N = 63;
 constexpr int SPILL_D0 = 43;   /* cells of h.d0, h.d1, h.d2 (spill's order below) */
+constexpr int SPILL_V0 = 0, SPILL_W2 = 5, SPILL_E0 = 12, SPILL_P0 = 15;   /* what salp::observation reads */
 struct SpillSlot {
     double* p;
     int stride = LANES;

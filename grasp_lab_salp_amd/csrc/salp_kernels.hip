@@ -809,15 +809,19 @@ __device__ __noinline__ bool lane_boundary_call(const RolloutArgs* a, double* sp
 // per wave, s_memtime cycles and loop iterations of each part of k_rollout's
 // chunk loop, summed over the launch's waves into g_roll_prof (read back by
 // salp_debug_rollout_prof): boundary + re-seat, full ticks, steady ticks,
-// settled ticks; and, of the two-role boundary (role_boundary), the finish
-// lanes' loads, their finish part, the plan lanes' plan, and the join (apply,
-// stores, spill).  RP_BOUNDARY keeps what is left of the boundary (publishing,
-// numbering the jobs).
+// settled ticks; and, of the four-role boundary (role_boundary), per role:
+// the finish wave's loads, finish_core, buffer rows, reset (after the barrier)
+// and join (apply, stores, spill); the observe wave's observation and its
+// obs_before rows, its action (c_action) and geometry cache (c_cache); the
+// plan wave's action, IK and direction; the draw wave's reset draw (c_draw).
+// RP_BOUNDARY keeps what is left of the boundary (publishing, numbering the
+// jobs).
 #ifndef SALP_ROLLOUT_PROF
 #define SALP_ROLLOUT_PROF 0
 #endif
-enum { RP_BOUNDARY, RP_FULL, RP_STEADY, RP_SETTLED, RP_BARRIER, RP_RESEAT, RP_B_LOAD, RP_B_FINISH, RP_B_PLAN,
-       RP_B_JOIN, RP_N };
+enum { RP_BOUNDARY, RP_FULL, RP_STEADY, RP_SETTLED, RP_BARRIER, RP_RESEAT, RP_B_LOAD, RP_B_FINISH, RP_B_ROWS,
+       RP_B_RESET, RP_B_JOIN, RP_O_OBS, RP_O_BEFORE, RP_P_ACTION, RP_P_IK, RP_P_DIR, RP_C_ACTION, RP_C_CACHE,
+       RP_C_DRAW, RP_N };
 __device__ unsigned long long g_roll_prof[2][RP_N];   // [cycles | iterations][part]
 struct RollProf {
     unsigned long long cyc[RP_N] = {}, its[RP_N] = {};
@@ -930,23 +934,44 @@ template <bool RAND>
     return tk;
 }
 
-// The env-step boundary of k_rollout<false, false> in two roles.  Inlined per
-// lane (lane_boundary), the boundary ran in all four waves at about 8 lanes
-// in 64, epilogue and prologue one after the other.  Here the workgroup's
-// boundary envs ("jobs": the set bits of the 256-bit need mask, in lane
-// order) are packed onto lanes: lane j < 128 finishes job j's env-step
-// (cold loads, finish_step, buffer rows, reset, obs_before: rollout_boundary's
-// first half), while lane 128 + j plans the env's next one from (seed, env id,
-// step count) alone: sp_action, salp::plan_step with the float32 geometry
-// cache written straight into the slot's column.  After a barrier the finish
-// lane applies the plan (salp::apply_step), stores the cold block and spills
-// the slot.  More than 128 jobs (a launch's first boundary) take two passes.
-// Zero-tick cycles chain as in rollout_boundary, at most four rounds per env:
-// a job whose new cycle has already ended stays on its finish lane for another
-// round, and the round count comes from LDS, so every wave executes the same
-// barriers.  Per-env results are rollout_boundary's.
+// The env-step boundary of k_rollout<false, false> in four roles, one wave
+// each.  Inlined per lane (lane_boundary), the boundary ran in all four waves
+// at about 8 lanes in 64, epilogue and prologue one after the other.  Here the
+// workgroup's boundary envs ("jobs": the set bits of the 256-bit need mask, in
+// lane order) are packed onto lanes, 64 to a pass, and job j of a pass is
+// lane j of every wave:
+//   wave 0, finish:  cold loads, unspill, salp::finish_core (finish_step
+//                    without its observation), the actions / rewards / dones
+//                    rows, a note for wave 1 (NOTE_*); after the barrier the
+//                    reset when the episode ended (draw from LDS),
+//                    salp::apply_step on the plan, store_cold, spill, flags,
+//                    mask atomics;
+//   wave 1, observe: the observation of the slot's state (Hot from the slot,
+//                    target and obstacles from the cold block: nobody writes
+//                    either before the barrier), the obs row, then sp_action
+//                    and the float32 geometry cache of the planned contraction
+//                    straight into the slot's column; after the barrier the
+//                    obs_before row of the step that begins: the same
+//                    observation when the episode goes on, that of the reset
+//                    state (salp::reset_observation, from the draw) when not;
+//   wave 2, plan:    sp_action, the IK of the rescaled yaw and the nozzle
+//                    direction of the env's next env-step, from (seed, env id,
+//                    step count) alone;
+//   wave 3, draw:    for every finishing job the reset draw of (seed, env id,
+//                    episode) into LDS, used only if the episode ended.
+// More than 64 jobs (a launch's first boundary starts every env) take up to
+// four passes.  Zero-tick cycles chain as in rollout_boundary, at most four
+// rounds per env: a job whose new cycle has already ended stays on its lanes
+// for another round; wave 0 stores the cold block and the slot after every
+// round, so every round reads the env the same way, and the round count comes
+// from LDS, so every wave executes the same barriers.  Per-env results are
+// rollout_boundary's.
 enum { FL_PENDING = 1, FL_ACTIVE = 2, FL_TICKING = 4 };   // s_flags, per slot
-constexpr int kRoleJobs = kBlock / 2;
+enum { NOTE_NONE, NOTE_SAME, NOTE_RESET };                // s_note: the env begins no step / one in the same episode / in a new one
+constexpr int kRoleJobs = 64;
+constexpr int kRolePasses = kBlock / kRoleJobs;
+constexpr int kDrawWords = 3 + 2 * SALP_MAX_OBSTACLES;    // floats: target (2), obstacle count, obstacles
+static_assert(kBlock == 4 * 64, "role_boundary: four waves, one role each");
 struct RoleLds {
     double* spill;            // s_spill
     double* cache32;          // s_cache32
@@ -957,54 +982,15 @@ struct RoleLds {
     uint64_t* amask;          // s_amask[b]: active, by lane; cleared here when max_steps ends an env
 };
 
-// First half of one round of a job: rollout_boundary's `fin` part and the
-// observation its `beg` part stores.  Returns whether the env begins a step.
-template <class ST>
-__device__ __forceinline__ bool role_finish(Hot& h, ST S, const Params& P, int64_t i, bool& pending, bool& active,
-                                            int64_t& steps, int64_t max_steps, const SalpRolloutBuffers& B,
-                                            double* reward_sum, float* o, bool& have_o) {
-    const bool fin = active && pending && !(h.ct < h.b2);
-    if (fin) {
-        SF(SALP_F_STEP_COUNT) = SF(SALP_F_STEP_COUNT) + 1.0;
-        salp::StepOut r = salp::finish_step<false>(h, S, P, i, o, nullptr);
-        const bool reset = r.terminated || r.truncated;
-        if (B.capacity > 0) {
-            const size_t slot = (size_t)(steps % B.capacity);
-            const size_t row = slot * (size_t)P.n + (size_t)i;
-            if (B.obs)
-                for (int k = 0; k < P.obs_dim; ++k) B.obs[row * P.obs_dim + k] = o[k];
-            if (B.actions) {
-                B.actions[row * 3 + 0] = (float)SF(SALP_F_ACT0);
-                B.actions[row * 3 + 1] = (float)SF(SALP_F_ACT1);
-                B.actions[row * 3 + 2] = (float)SF(SALP_F_ACT2);
-            }
-            if (B.rewards) B.rewards[row] = (float)r.reward;
-            if (B.dones) B.dones[row] = (uint8_t)((r.terminated ? 1 : 0) | (r.truncated ? 2 : 0));
-        }
-        if (reward_sum) reward_sum[i] += r.reward;
-        ++steps;
-        pending = false;
-        if (reset) salp::reset_env_philox(h, S, P, i, B.obs_before ? o : nullptr);
-        have_o = true;
-        if (max_steps > 0 && steps >= max_steps) active = false;
-    }
-    const bool beg = active && !pending;
-    if (beg && B.obs_before) {
-        if (!have_o) {
-            const salp::Rot Rt = salp::rot_zyx(h.e0, h.e1, h.e2);
-            salp::observation(h, Rt, S, P, i, o);
-            have_o = true;
-        }
-        if (B.capacity > 0) {
-            const size_t row = (size_t)(steps % B.capacity) * (size_t)P.n + (size_t)i;
-            for (int k = 0; k < P.obs_dim; ++k) B.obs_before[row * P.obs_dim + k] = o[k];
-        }
-    }
-    return beg;
-}
-
 __device__ __forceinline__ uint64_t pack_floats(float lo, float hi) {
     return (uint64_t)__float_as_uint(lo) | ((uint64_t)__float_as_uint(hi) << 32);
+}
+
+// One observation into its buffer row; constant indices keep o in registers.
+__device__ __forceinline__ void store_obs_row(float* row, const float* o, int obs_dim) {
+#pragma unroll
+    for (int k = 0; k < SALP_OBS_DIM_MAX; ++k)
+        if (k < obs_dim) row[k] = o[k];
 }
 
 // Every lane of the workgroup calls this once per chunk, after it has written
@@ -1014,15 +1000,15 @@ __device__ __forceinline__ uint64_t pack_floats(float lo, float hi) {
 // and both masks are what the re-seat reads.
 __device__ __forceinline__ void role_boundary(const RoleLds L, const int b, const int lane, const int64_t base,
                                               const bool need, RollProf& prof) {
-    __shared__ uint64_t s_need[2][kBlock / 64];   // need ballots per wave (double-buffered like s_mask)
-    __shared__ uint32_t s_again[2][2][4];         // [b][pass][round]: some job of the pass takes another round
-    // Per job: the plan (two words of packed action floats, an1, an2; the
-    // direction goes to the slot's own d cells), then, from the finish lane to
-    // the plan lane of the next round: the step count to plan for, and whether to.
-    __shared__ uint64_t s_plan[4][kRoleJobs];
+    __shared__ uint64_t s_need[2][kBlock / 64];        // need ballots per wave (double-buffered like s_mask)
+    __shared__ uint32_t s_again[2][kRolePasses][4];    // [b][pass][round]: some job of the pass takes another round
+    __shared__ uint64_t s_plan[4][kRoleJobs];          // plan -> finish: packed action floats (2 words), an1, an2
+    __shared__ float s_draw[kRoleJobs][kDrawWords];    // draw -> finish, observe: the reset draw of a finishing job
+    __shared__ uint8_t s_note[kRoleJobs];              // finish -> observe: NOTE_*, which obs_before row to store
+    __shared__ uint8_t s_live[kRoleJobs];              // finish -> the others: the job takes another round
     const uint64_t nb = __ballot(need);
     if ((lane & 63) == 0) s_need[b][lane >> 6] = nb;
-    if (lane < 8) (&s_again[b][0][0])[lane] = 0u;
+    if (lane < kRolePasses * 4) (&s_again[b][0][0])[lane] = 0u;
     prof.lap(RP_BOUNDARY);
     __syncthreads();
     prof.lap(RP_BARRIER);
@@ -1033,7 +1019,7 @@ __device__ __forceinline__ void role_boundary(const RoleLds L, const int b, cons
         nm[w] = s_need[b][w];
         n_jobs += __popcll(nm[w]);
     }
-    const bool fin_role = lane < kRoleJobs;
+    const int role = __builtin_amdgcn_readfirstlane(lane >> 6);
     const int jr = lane & (kRoleJobs - 1);
     for (int p = 0; p * kRoleJobs < n_jobs; ++p) {
         const int j = p * kRoleJobs + jr;
@@ -1045,49 +1031,125 @@ __device__ __forceinline__ void role_boundary(const RoleLds L, const int b, cons
         }
         const int64_t i = base + js;
         const salp::SpillSlot sp{L.spill + js};
-        // finish lane: the env, in registers for all the job's rounds
+        // finish wave: the env, in registers for all the job's rounds
         salp::ColdRegs<false> C;
         Hot hb;
-        float o[SALP_OBS_DIM_MAX];
-        bool have_o = false, pending = false, active = false, live = fin_role && has;
+        bool pending = false, active = false;
         int64_t steps = 0;
-        // plan lane: whether the job's env begins a step this round, and its step count then
-        bool go = false;
-        double sc = 0.0;
+        float o[SALP_OBS_DIM_MAX];   // observe wave: the slot's observation
+        bool live = has;             // the job takes this round
         prof.lap(RP_BOUNDARY);
-        if (has) {
+        if (role == 0 && has) {
             const RolloutArgs a = fresh_args();
             const int fl = L.flags[js];
-            if (fin_role) {
-                salp::load_cold<false>(C, a.S, a.P, i);
-                salp::unspill<false>(hb, sp, a.P, (uint64_t)(a.P.env_offset + i));
-                pending = (fl & FL_PENDING) != 0;
-                active = (fl & FL_ACTIVE) != 0;
-                steps = L.steps[js];
-            } else {
-                const bool fin = (fl & FL_ACTIVE) && (fl & FL_PENDING) && !(fl & FL_TICKING);
-                const int64_t st = L.steps[js] + (fin ? 1 : 0);
-                go = !(fin && a.max_steps > 0 && st >= a.max_steps);   // else max_steps ends the env: no plan
-                sc = salp::sref((const double*)a.S, a.P, i, SALP_F_STEP_COUNT) + (fin ? 1.0 : 0.0);
-            }
+            salp::load_cold<false>(C, a.S, a.P, i);
+            salp::unspill<false>(hb, sp, a.P, (uint64_t)(a.P.env_offset + i));
+            pending = (fl & FL_PENDING) != 0;
+            active = (fl & FL_ACTIVE) != 0;
+            steps = L.steps[js];
         }
         prof.lap(RP_B_LOAD);
         for (int r = 0;; ++r) {
-            bool beg = false;
-            if (fin_role) {
-                if (live) {
+            // observe, plan, cycle: what the round does with the job, from the slot's flags and step count
+            bool fin = false, go = false;
+            int64_t st = 0;
+            if (role != 0 && live) {
+                const RolloutArgs a = fresh_args();
+                const int fl = L.flags[js];
+                fin = (fl & FL_ACTIVE) && (fl & FL_PENDING) && !(fl & FL_TICKING);
+                st = L.steps[js];
+                go = !(fin && a.max_steps > 0 && st + 1 >= a.max_steps);   // else max_steps ends the env: no plan
+            }
+            bool beg = false, rst = false;   // finish wave: the env begins a step; its episode ended
+            if (role == 0) {
+                const bool fin0 = live && active && pending && !(hb.ct < hb.b2);
+                salp::StepOut so{};
+                if (fin0) {
                     const RolloutArgs a = fresh_args();
-                    beg = role_finish(hb, &C, a.P, i, pending, active, steps, a.max_steps, a.B, a.reward_sum, o,
-                                      have_o);
+                    salp::sref(&C, a.P, i, SALP_F_STEP_COUNT) = salp::sref(&C, a.P, i, SALP_F_STEP_COUNT) + 1.0;
+                    so = salp::finish_core(hb, &C, a.P, i);
                 }
                 prof.lap(RP_B_FINISH);
-            } else {
+                if (fin0) {
+                    const RolloutArgs a = fresh_args();
+                    rst = so.terminated || so.truncated;
+                    if (a.B.capacity > 0) {
+                        const size_t row = (size_t)(steps % a.B.capacity) * (size_t)a.P.n + (size_t)i;
+                        if (a.B.actions) {
+                            a.B.actions[row * 3 + 0] = (float)salp::sref(&C, a.P, i, SALP_F_ACT0);
+                            a.B.actions[row * 3 + 1] = (float)salp::sref(&C, a.P, i, SALP_F_ACT1);
+                            a.B.actions[row * 3 + 2] = (float)salp::sref(&C, a.P, i, SALP_F_ACT2);
+                        }
+                        if (a.B.rewards) a.B.rewards[row] = (float)so.reward;
+                        if (a.B.dones)
+                            a.B.dones[row] = (uint8_t)((so.terminated ? 1 : 0) | (so.truncated ? 2 : 0));
+                    }
+                    if (a.reward_sum) a.reward_sum[i] += so.reward;
+                    ++steps;
+                    pending = false;
+                    if (a.max_steps > 0 && steps >= a.max_steps) active = false;
+                }
+                if (live) {
+                    beg = active && !pending;
+                    s_note[jr] = beg ? (rst ? NOTE_RESET : NOTE_SAME) : NOTE_NONE;
+                }
+                prof.lap(RP_B_ROWS);
+            } else if (role == 1) {
+                if (live) {
+                    const RolloutArgs a = fresh_args();
+                    // a finishing job: the ended step's observation, which is the next step's
+                    // obs_before too unless the episode ended; a job that only begins: obs_before
+                    if (fin ? (a.B.obs != nullptr || a.B.obs_before != nullptr) : a.B.obs_before != nullptr) {
+                        Hot ho;
+                        ho.v0 = sp[salp::SPILL_V0];
+                        ho.v1 = sp[salp::SPILL_V0 + 1];
+                        ho.w2 = sp[salp::SPILL_W2];
+                        ho.e0 = sp[salp::SPILL_E0];
+                        ho.e1 = sp[salp::SPILL_E0 + 1];
+                        ho.e2 = sp[salp::SPILL_E0 + 2];
+                        ho.p0 = sp[salp::SPILL_P0];
+                        ho.p1 = sp[salp::SPILL_P0 + 1];
+                        const salp::Rot Rt = salp::rot_zyx(ho.e0, ho.e1, ho.e2);
+                        salp::observation(ho, Rt, (const double*)a.S, a.P, i, o);
+                        if (fin && a.B.obs && a.B.capacity > 0) {
+                            const size_t row = (size_t)(st % a.B.capacity) * (size_t)a.P.n + (size_t)i;
+                            store_obs_row(a.B.obs + row * a.P.obs_dim, o, a.P.obs_dim);
+                        }
+                    }
+                }
+                prof.lap(RP_O_OBS);
+                float a0 = 0.0f;
                 if (go) {
                     const RolloutArgs a = fresh_args();
+                    const double sc =
+                        salp::sref((const double*)a.S, a.P, i, SALP_F_STEP_COUNT) + (fin ? 1.0 : 0.0);
                     float act[3];
                     sp_action(a.P.seed, (uint64_t)(a.P.env_offset + i), (uint64_t)sc, act);
-                    const salp::StepPlan pl =
-                        salp::plan_step(a.P, act[0], act[1], act[2], salp::Cache32{L.cache32 + js});
+                    a0 = act[0];
+                }
+                prof.lap(RP_C_ACTION);
+                if (go) {
+                    const RolloutArgs a = fresh_args();
+                    salp::plan_cache(a.P, a0, salp::Cache32{L.cache32 + js});
+                }
+                prof.lap(RP_C_CACHE);
+            } else if (role == 2) {
+                salp::StepPlan pl{};
+                if (go) {
+                    const RolloutArgs a = fresh_args();
+                    const double sc =
+                        salp::sref((const double*)a.S, a.P, i, SALP_F_STEP_COUNT) + (fin ? 1.0 : 0.0);
+                    float act[3];
+                    sp_action(a.P.seed, (uint64_t)(a.P.env_offset + i), (uint64_t)sc, act);
+                    pl.a0 = act[0];
+                    pl.a1 = act[1];
+                    pl.a2 = act[2];
+                }
+                prof.lap(RP_P_ACTION);
+                if (go) salp::plan_angles(pl);
+                prof.lap(RP_P_IK);
+                if (go) {
+                    salp::plan_direction(pl);
                     s_plan[0][jr] = pack_floats(pl.a0, pl.a1);
                     s_plan[1][jr] = pack_floats(pl.a2, 0.0f);
                     s_plan[2][jr] = (uint64_t)__double_as_longlong(pl.an1);
@@ -1098,57 +1160,86 @@ __device__ __forceinline__ void role_boundary(const RoleLds L, const int b, cons
 #pragma unroll
                     for (int k = 0; k < 3; ++k) sp[salp::SPILL_D0 + k] = pl.d[k];
                 }
-                prof.lap(RP_B_PLAN);
+                prof.lap(RP_P_DIR);
+            } else {
+                if (fin) {
+                    // the draw is a function of (seed, env id, episode) alone; the episode may not end
+                    const RolloutArgs a = fresh_args();
+                    const uint64_t episode = (uint64_t)salp::sref((const double*)a.S, a.P, i, SALP_F_EPISODE);
+                    // drawn in place: the rejection loop indexes the obstacles it has so far
+                    float* const rec = s_draw[jr];
+                    rec[2] = (float)salp::draw_reset(a.P, (uint64_t)(a.P.env_offset + i), episode, rec, rec + 3);
+                }
+                prof.lap(RP_C_DRAW);
             }
             prof.lap(RP_BOUNDARY);
             __syncthreads();
             prof.lap(RP_BARRIER);
-            if (live) {
-                const RolloutArgs a = fresh_args();
-                if (beg) {
-                    salp::StepPlan pl;
-                    const uint64_t w0 = s_plan[0][jr], w1 = s_plan[1][jr];
-                    pl.a0 = __uint_as_float((uint32_t)w0);
-                    pl.a1 = __uint_as_float((uint32_t)(w0 >> 32));
-                    pl.a2 = __uint_as_float((uint32_t)w1);
-                    pl.an1 = __longlong_as_double((long long)s_plan[2][jr]);
-                    pl.an2 = __longlong_as_double((long long)s_plan[3][jr]);
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) pl.d[k] = sp[salp::SPILL_D0 + k];
-                    salp::apply_step(hb, &C, a.P, i, pl);
-                    pending = true;
+            if (role == 0) {
+                if (live && rst) {
+                    const RolloutArgs a = fresh_args();
+                    const float* const rec = s_draw[jr];
+                    salp::reset_env(hb, &C, a.P, i, rec, rec + 3, (int)rec[2], nullptr);   // the observe wave observes
                 }
-                // a zero-tick cycle has ended already: its env-step finishes in the next round
-                const bool again = r < 3 && active && pending && !(hb.ct < hb.b2);
-                if (again) {
-                    s_again[b][p][r] = 1u;
-                    s_plan[0][jr] =
-                        (uint64_t)__double_as_longlong(salp::sref(&C, a.P, i, SALP_F_STEP_COUNT) + 1.0);
-                    s_plan[1][jr] = (a.max_steps > 0 && steps + 1 >= a.max_steps) ? 0u : 1u;
-                } else {
-                    s_plan[1][jr] = 0u;
+                prof.lap(RP_B_RESET);
+                if (live) {
+                    const RolloutArgs a = fresh_args();
+                    if (beg) {
+                        salp::StepPlan pl;
+                        const uint64_t w0 = s_plan[0][jr], w1 = s_plan[1][jr];
+                        pl.a0 = __uint_as_float((uint32_t)w0);
+                        pl.a1 = __uint_as_float((uint32_t)(w0 >> 32));
+                        pl.a2 = __uint_as_float((uint32_t)w1);
+                        pl.an1 = __longlong_as_double((long long)s_plan[2][jr]);
+                        pl.an2 = __longlong_as_double((long long)s_plan[3][jr]);
+#pragma unroll
+                        for (int k = 0; k < 3; ++k) pl.d[k] = sp[salp::SPILL_D0 + k];
+                        salp::apply_step(hb, &C, a.P, i, pl);
+                        pending = true;
+                    }
+                    // a zero-tick cycle has ended already: its env-step finishes in the next
+                    // round, which reads the env from the cold block and the slot like the first
+                    const bool again = r < 3 && active && pending && !(hb.ct < hb.b2);
                     salp::store_cold<false>(C, a.S, a.P, i);
                     salp::spill<false>(hb, sp);
                     L.flags[js] = (uint8_t)((pending ? FL_PENDING : 0) | (active ? FL_ACTIVE : 0));
                     L.steps[js] = steps;
-                    const uint64_t bit = 1ull << (jl & 63);
-                    if (unsteady(hb, a.P, active)) atomicOr((unsigned long long*)&L.mask[jl >> 6], bit);
-                    if (!active) atomicAnd((unsigned long long*)&L.amask[jl >> 6], ~bit);
-                    live = false;
+                    s_live[jr] = again ? 1 : 0;
+                    if (again) {
+                        s_again[b][p][r] = 1u;
+                    } else {
+                        const uint64_t bit = 1ull << (jl & 63);
+                        if (unsteady(hb, a.P, active)) atomicOr((unsigned long long*)&L.mask[jl >> 6], bit);
+                        if (!active) atomicAnd((unsigned long long*)&L.amask[jl >> 6], ~bit);
+                        live = false;
+                    }
                 }
+                prof.lap(RP_B_JOIN);
+            } else if (role == 1) {
+                if (live) {
+                    const RolloutArgs a = fresh_args();
+                    const int note = fin ? s_note[jr] : NOTE_SAME;   // need without a finish: the env begins a step
+                    if (note != NOTE_NONE && a.B.obs_before && a.B.capacity > 0) {
+                        if (note == NOTE_RESET) {
+                            const float* const rec = s_draw[jr];
+                            salp::reset_observation(a.P, rec, rec + 3, (int)rec[2], o);
+                        }
+                        const size_t row =
+                            (size_t)((st + (fin ? 1 : 0)) % a.B.capacity) * (size_t)a.P.n + (size_t)i;
+                        store_obs_row(a.B.obs_before + row * a.P.obs_dim, o, a.P.obs_dim);
+                    }
+                }
+                prof.lap(RP_O_BEFORE);
             }
-            prof.lap(RP_B_JOIN);
+            prof.lap(RP_BOUNDARY);
             __syncthreads();
             prof.lap(RP_BARRIER);
             if (r == 3 || !s_again[b][p][r]) break;
-            go = false;
-            if (!fin_role && has && s_plan[1][jr] != 0u) {
-                go = true;
-                sc = __longlong_as_double((long long)s_plan[0][jr]);
-            }
+            if (role != 0) live = has && s_live[jr] != 0;
         }
     }
 }
+
 
 template <bool RAND, bool POL>
 __global__ __launch_bounds__(kBlock) void k_rollout(RolloutArgs A) {
@@ -1156,7 +1247,7 @@ __global__ __launch_bounds__(kBlock) void k_rollout(RolloutArgs A) {
     const Params& P = A.P;
     const int64_t base = (int64_t)blockIdx.x * blockDim.x;
     const int lane = (int)threadIdx.x;
-    constexpr bool kRoles = !RAND && !POL;   // the plain rollout: two-role boundary (role_boundary)
+    constexpr bool kRoles = !RAND && !POL;   // the plain rollout: four-role boundary (role_boundary)
     __shared__ double s_cache32[salp::C32_N * salp::LANES];
     __shared__ double s_spill[salp::SPILL_N * salp::LANES];
     __shared__ int64_t s_steps[kBlock];
@@ -1195,7 +1286,7 @@ __global__ __launch_bounds__(kBlock) void k_rollout(RolloutArgs A) {
         bool uns = (tk & TK_UNSTEADY) != 0;
         if constexpr (kRoles) {
             const int b = (int)(c & 1);
-            // publish the slot, then the two-role boundary (role_boundary), whose
+            // publish the slot, then the four-role boundary (role_boundary), whose
             // last barrier is the re-seat's
             s_steps[s] = steps;
             s_flags[s] = (uint8_t)((pending ? FL_PENDING : 0) | (active ? FL_ACTIVE : 0) |

@@ -21,11 +21,14 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 from grasp_lab_salp_amd import _lib  # noqa: E402
 from grasp_lab_salp_amd.batched_env import BatchedSalpEnv  # noqa: E402
 
-# the last four: inside k_rollout<false, false>'s two-role boundary (finish
-# lanes: cold loads + unspill, the finish part; plan lanes: the plan; finish
-# lanes again: apply + stores + spill); "boundary" is the rest of it
-PARTS = ["boundary", "full", "steady", "settled", "barrier", "reseat", "b_load", "b_finish", "b_plan", "b_join"]
-
+# after "reseat": inside k_rollout<false, false>'s four-role boundary, per role
+# (finish wave: cold loads + unspill, finish_core, buffer rows, reset after the
+# barrier, join = apply + stores + spill; observe wave: observation + obs row,
+# obs_before row (with the reset state's observation), c_action, c_cache = its
+# sp_action and geometry cache; plan wave: action, IK, direction; draw wave:
+# c_draw); "boundary" is the rest of it
+PARTS = ["boundary", "full", "steady", "settled", "barrier", "reseat", "b_load", "b_finish", "b_rows", "b_reset",
+         "b_join", "o_obs", "o_before", "p_action", "p_ik", "p_dir", "c_action", "c_cache", "c_draw"]
 
 def main():
     n, budget, cap = 65536, 8192, 16

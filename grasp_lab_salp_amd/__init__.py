@@ -14,5 +14,8 @@ without torch or a GPU):
   :class:`grasp_lab_salp_amd.recurrent_ppo.RecurrentPPO`,
   :class:`grasp_lab_salp_amd.sac.SAC` — on-device learners (SAC is the one
   src/train_robot.py trains with).
+* :mod:`grasp_lab_salp_amd.callbacks` — SB3-named training callbacks for SAC
+  (metrics, evaluation, checkpoints); :mod:`grasp_lab_salp_amd.metrics` — the
+  episode window and evaluation bookkeeping they keep on the device.
 """
 __version__ = "0.1.0"

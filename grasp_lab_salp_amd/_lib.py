@@ -235,6 +235,43 @@ class SalpSacNetBackward(ctypes.Structure):
     ]
 
 
+EPWIN_COLS = 20           # include/salp.h SALP_EPWIN_COLS
+EPWIN_MAX_WINDOW = 1024   # include/salp.h SALP_EPWIN_MAX_WINDOW
+EPSUM_DIM = 84            # include/salp.h SALP_EPSUM_DIM
+
+
+class SalpEpisodeWindow(ctypes.Structure):
+    _fields_ = [
+        ("window", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("rows", ctypes.c_void_p),
+        ("count", ctypes.c_void_p),
+    ]
+
+
+class SalpEpisodePush(ctypes.Structure):
+    _fields_ = [
+        ("n_envs", ctypes.c_int64),
+        ("info", ctypes.c_void_p),
+        ("terminated", ctypes.c_void_p),
+        ("truncated", ctypes.c_void_p),
+        ("skip", ctypes.c_void_p),
+    ]
+
+
+class SalpEvalState(ctypes.Structure):
+    _fields_ = [
+        ("n_envs", ctypes.c_int64),
+        ("target", ctypes.c_void_p),
+        ("offset", ctypes.c_void_p),
+        ("done_count", ctypes.c_void_p),
+        ("ep_return", ctypes.c_void_p),
+        ("ep_len", ctypes.c_void_p),
+        ("success", ctypes.c_void_p),
+        ("remaining", ctypes.c_void_p),
+    ]
+
+
 class SalpTraceBuffer(ctypes.Structure):
     _fields_ = [
         ("max_samples", ctypes.c_int64),
@@ -307,6 +344,10 @@ SIGNATURES = {
     "salp_sac_net_workspace_floats": (ctypes.c_int64, [ctypes.c_int64] + [ctypes.c_int] * 4),
     "salp_sac_net_forward": (ctypes.c_int, [ctypes.POINTER(SalpSacNetForward), _V]),
     "salp_sac_net_backward": (ctypes.c_int, [ctypes.POINTER(SalpSacNetBackward), _V]),
+    "salp_episode_window_push": (ctypes.c_int, [ctypes.POINTER(SalpEpisodeWindow), ctypes.POINTER(SalpEpisodePush),
+                                                _V]),
+    "salp_episode_window_summary": (ctypes.c_int, [ctypes.POINTER(SalpEpisodeWindow), _V, _V]),
+    "salp_eval_account": (ctypes.c_int, [ctypes.POINTER(SalpEvalState), ctypes.POINTER(SalpEpisodePush), _V]),
 }
 
 

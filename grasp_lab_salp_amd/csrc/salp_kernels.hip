@@ -2652,6 +2652,14 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t salp_sac_net_fwd_lau
                                                                                      void* stream);
 extern "C" __attribute__((visibility("hidden"))) hipError_t salp_sac_net_bwd_launch(const SalpSacNetBackward* b,
                                                                                      void* stream);
+extern "C" __attribute__((visibility("hidden"))) hipError_t salp_epwin_push_launch(const SalpEpisodeWindow* w,
+                                                                                    const SalpEpisodePush* p,
+                                                                                    void* stream);
+extern "C" __attribute__((visibility("hidden"))) hipError_t salp_epwin_summary_launch(const SalpEpisodeWindow* w,
+                                                                                       double* out, void* stream);
+extern "C" __attribute__((visibility("hidden"))) hipError_t salp_eval_account_launch(const SalpEvalState* s,
+                                                                                      const SalpEpisodePush* p,
+                                                                                      void* stream);
 
 extern "C" {
 
@@ -3296,6 +3304,40 @@ int salp_sac_net_backward(const SalpSacNetBackward* b, void* stream) {
     if (b->dx1 && b->d1 == 0) return fail(nullptr, SALP_EINVAL, "salp_sac_net_backward: dx1 needs d1 > 0");
     if (!b->workspace) return fail(nullptr, SALP_EINVAL, "salp_sac_net_backward: null workspace");
     return check_hip(nullptr, salp_sac_net_bwd_launch(b, stream), "k_sac_net_bwd");
+}
+
+static bool epwin_ok(const SalpEpisodeWindow* w) {
+    return w && w->window >= 1 && w->window <= SALP_EPWIN_MAX_WINDOW && w->rows && w->count;
+}
+
+static bool eppush_ok(const SalpEpisodePush* p) {
+    return p && p->n_envs >= 1 && p->info && p->terminated && p->truncated;
+}
+
+int salp_episode_window_push(const SalpEpisodeWindow* w, const SalpEpisodePush* p, void* stream) {
+    if (!epwin_ok(w))
+        return fail(nullptr, SALP_EINVAL, "salp_episode_window_push: window must be in 1 .. 1024, rows and count set");
+    if (!eppush_ok(p))
+        return fail(nullptr, SALP_EINVAL, "salp_episode_window_push: n_envs >= 1 and info, terminated, truncated set");
+    return check_hip(nullptr, salp_epwin_push_launch(w, p, stream), "k_epwin_push");
+}
+
+int salp_episode_window_summary(const SalpEpisodeWindow* w, double* out, void* stream) {
+    if (!epwin_ok(w))
+        return fail(nullptr, SALP_EINVAL,
+                    "salp_episode_window_summary: window must be in 1 .. 1024, rows and count set");
+    if (!out) return fail(nullptr, SALP_EINVAL, "salp_episode_window_summary: null out");
+    return check_hip(nullptr, salp_epwin_summary_launch(w, out, stream), "k_epwin_summary");
+}
+
+int salp_eval_account(const SalpEvalState* s, const SalpEpisodePush* p, void* stream) {
+    if (!s || s->n_envs < 1 || s->n_envs > INT32_MAX * (int64_t)256)
+        return fail(nullptr, SALP_EINVAL, "salp_eval_account: n_envs must be positive");
+    if (!s->target || !s->offset || !s->done_count || !s->ep_return || !s->ep_len || !s->success || !s->remaining)
+        return fail(nullptr, SALP_EINVAL, "salp_eval_account: null state buffer");
+    if (!eppush_ok(p) || p->n_envs != s->n_envs)
+        return fail(nullptr, SALP_EINVAL, "salp_eval_account: the step must be of the state's n_envs, buffers set");
+    return check_hip(nullptr, salp_eval_account_launch(s, p, stream), "k_eval_account");
 }
 
 }  // extern "C"

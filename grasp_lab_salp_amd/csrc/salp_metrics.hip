@@ -1,0 +1,216 @@
+// salp_metrics.hip — episode metrics and evaluation bookkeeping on the device (gfx950).
+//
+// What it restates: the per-env-step host work of the reference's callbacks,
+// which walk a Python list of info dicts after every vec-env step:
+//
+//   k_epwin_push      src/tensorboard_callback.py:36-123: a deque(maxlen=window)
+//                     per metric, appended to for every env whose episode ended,
+//                     in env order — here one ring of rows and one counter
+//   k_epwin_summary   :131-205: mean / np.std / min / max of every deque, the
+//                     distance per cycle and the cycles to success
+//   k_eval_account    stable_baselines3 evaluate_policy over a vector env: env i
+//                     contributes its first target[i] episodes
+//
+// Everything is enqueued on the caller's stream, nothing allocates or
+// synchronises, and there is no floating-point atomic: the push ranks its
+// finishers with ballots and an integer scan, the summary adds in one fixed
+// order, and the only atomic is the integer countdown of the evaluation.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+
+#include "../../include/salp.h"
+
+namespace {
+
+constexpr int kPushBlock = 1024;              // one workgroup walks all envs
+constexpr int kPushWaves = kPushBlock / 64;
+constexpr int kSumBlock = 64;                 // one wave per statistic
+constexpr int kEvalBlock = 256;
+constexpr int kInfoCols = SALP_EPWIN_COLS - 4;   // SALP_INFO_PATH_LENGTH .. SALP_INFO_AVG_R_OBSTACLE
+
+static_assert(SALP_INFO_AVG_R_OBSTACLE - SALP_INFO_PATH_LENGTH + 1 == kInfoCols, "row layout");
+static_assert(SALP_EPSUM_DIM == 1 + 4 * SALP_EPWIN_COLS + 3, "summary layout");
+static_assert(SALP_EPWIN_MAX_WINDOW <= INT32_MAX, "window is an int32");
+
+__device__ __forceinline__ bool finishes(const SalpEpisodePush& p, int64_t e) {
+    return (p.terminated[e] | p.truncated[e]) != 0 && !(p.skip && p.skip[e] != 0);
+}
+
+// Pass 1 counts the finishers D; pass 2 walks the envs again in chunks of one
+// env per thread, ranks each chunk's finishers (ballot inside a wave, the 16
+// wave totals through LDS) on top of the chunks before it, and the r-th
+// finisher writes episode count + r into row (count + r) % window — unless
+// D > window and it is not among the last `window`, whose rows are all distinct.
+__global__ __launch_bounds__(kPushBlock) void k_epwin_push(SalpEpisodeWindow w, SalpEpisodePush p) {
+    __shared__ int64_t tot[2][kPushWaves];
+    const int lane = threadIdx.x % 64, wave = threadIdx.x / 64;
+    const int64_t n = p.n_envs;
+    const int64_t chunks = (n + kPushBlock - 1) / kPushBlock;
+    const int64_t count0 = w.count[0];
+
+    int64_t mine = 0;
+    for (int64_t e = threadIdx.x; e < n; e += kPushBlock) mine += finishes(p, e) ? 1 : 0;
+    for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
+    if (lane == 0) tot[0][wave] = mine;
+    __syncthreads();
+    int64_t D = 0;
+    for (int k = 0; k < kPushWaves; ++k) D += tot[0][k];
+    __syncthreads();   // tot[0] is written again by chunk 0
+    if (D == 0) return;
+    const int64_t first = D > w.window ? D - w.window : 0;   // finishers before this rank are overwritten: skipped
+
+    int64_t before = 0;   // finishers in the chunks already walked
+    for (int64_t c = 0; c < chunks; ++c) {
+        const int64_t e = c * kPushBlock + threadIdx.x;
+        const bool fin = e < n && finishes(p, e);
+        const unsigned long long m = __ballot(fin);
+        int64_t* t = tot[c & 1];
+        if (lane == 0) t[wave] = __popcll(m);
+        __syncthreads();   // the other buffer is next written after the next barrier, when every read of it is over
+        int64_t below = 0, all = 0;
+        for (int k = 0; k < kPushWaves; ++k) {
+            const int64_t v = t[k];
+            below += k < wave ? v : 0;
+            all += v;
+        }
+        if (fin) {
+            const int64_t r = before + below + __popcll(m & ((1ull << lane) - 1ull));
+            if (r >= first) {
+                const int64_t ep = count0 + r;
+                double* row = w.rows + (ep % w.window) * SALP_EPWIN_COLS;
+                const double* info = p.info + e * SALP_INFO_DIM;
+                const bool term = p.terminated[e] != 0;
+                // bit copies: through integers, so a NaN keeps its payload
+                const uint64_t* src = reinterpret_cast<const uint64_t*>(info);
+                uint64_t* dst = reinterpret_cast<uint64_t*>(row);
+                dst[0] = src[SALP_INFO_EP_RETURN];
+                dst[1] = src[SALP_INFO_EP_LEN];
+                row[2] = term ? 1.0 : 0.0;
+                row[3] = (!term && p.truncated[e] != 0) ? 1.0 : 0.0;
+                for (int k = 0; k < kInfoCols; ++k) dst[4 + k] = src[SALP_INFO_PATH_LENGTH + k];
+            }
+        }
+        before += all;
+    }
+    // every thread read count[0] before the first barrier
+    if (threadIdx.x == 0) w.count[0] = count0 + D;
+}
+
+// A wave's sum in one fixed order: each lane adds its rows in ascending order, then the butterfly.
+__device__ __forceinline__ double wave_sum(double v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ double wave_min(double v) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const double u = __shfl_xor(v, o, 64);
+        v = u < v ? u : v;
+    }
+    return v;
+}
+__device__ __forceinline__ double wave_max(double v) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const double u = __shfl_xor(v, o, 64);
+        v = u > v ? u : v;
+    }
+    return v;
+}
+
+// Block c < SALP_EPWIN_COLS: column c's mean, two-pass population standard
+// deviation, min and max.  Block SALP_EPWIN_COLS: mean(path_length / ep_len).
+// Block SALP_EPWIN_COLS + 1: mean ep_len over success rows and their number.
+__global__ __launch_bounds__(kSumBlock) void k_epwin_summary(SalpEpisodeWindow w, double* __restrict__ out) {
+    const int lane = threadIdx.x;
+    const int c = blockIdx.x;
+    const int64_t cnt = w.count[0];
+    const int n = (int)(cnt < w.window ? cnt : w.window);   // rows 0 .. n - 1 hold episodes
+    const double nan = __longlong_as_double(0x7FF8000000000000ll);
+    const double* rows = w.rows;
+    if (c == 0 && lane == 0) out[0] = (double)n;
+    if (c < SALP_EPWIN_COLS) {
+        double s = 0.0, lo = INFINITY, hi = -INFINITY;
+        for (int r = lane; r < n; r += 64) {
+            const double v = rows[(int64_t)r * SALP_EPWIN_COLS + c];
+            s += v;
+            lo = v < lo ? v : lo;
+            hi = v > hi ? v : hi;
+        }
+        const double mean = wave_sum(s) / (double)n;
+        double q = 0.0;
+        for (int r = lane; r < n; r += 64) {
+            const double d = rows[(int64_t)r * SALP_EPWIN_COLS + c] - mean;
+            q += d * d;
+        }
+        const double var = wave_sum(q) / (double)n;
+        lo = wave_min(lo);
+        hi = wave_max(hi);
+        if (lane == 0) {
+            double* o = out + 1 + 4 * c;
+            o[0] = n ? mean : nan;
+            o[1] = n ? sqrt(var) : nan;
+            o[2] = n ? lo : nan;
+            o[3] = n ? hi : nan;
+        }
+    } else if (c == SALP_EPWIN_COLS) {
+        double s = 0.0;
+        for (int r = lane; r < n; r += 64)
+            s += rows[(int64_t)r * SALP_EPWIN_COLS + 4] / rows[(int64_t)r * SALP_EPWIN_COLS + 1];
+        s = wave_sum(s);
+        if (lane == 0) out[1 + 4 * SALP_EPWIN_COLS] = n ? s / (double)n : nan;
+    } else {
+        double s = 0.0, k = 0.0;
+        for (int r = lane; r < n; r += 64) {
+            const bool ok = rows[(int64_t)r * SALP_EPWIN_COLS + 2] == 1.0;
+            s += ok ? rows[(int64_t)r * SALP_EPWIN_COLS + 1] : 0.0;
+            k += ok ? 1.0 : 0.0;
+        }
+        s = wave_sum(s);
+        k = wave_sum(k);   // whole numbers <= 1024: exact
+        if (lane == 0) {
+            out[2 + 4 * SALP_EPWIN_COLS] = k > 0.0 ? s / k : nan;
+            out[3 + 4 * SALP_EPWIN_COLS] = n ? k : nan;
+        }
+    }
+}
+
+// One thread per env; an env only ever touches its own slots.
+__global__ __launch_bounds__(kEvalBlock) void k_eval_account(SalpEvalState s, SalpEpisodePush p) {
+    const int64_t i = (int64_t)blockIdx.x * kEvalBlock + threadIdx.x;
+    if (i >= s.n_envs) return;
+    if ((p.terminated[i] | p.truncated[i]) == 0) return;
+    const int32_t d = s.done_count[i];
+    if (d >= s.target[i]) return;   // SB3 ignores an env's episodes past its target
+    const int64_t slot = s.offset[i] + d;
+    const double* info = p.info + i * SALP_INFO_DIM;
+    s.ep_return[slot] = info[SALP_INFO_EP_RETURN];
+    s.ep_len[slot] = info[SALP_INFO_EP_LEN];
+    s.success[slot] = p.terminated[i] != 0 ? 1 : 0;
+    s.done_count[i] = d + 1;
+    atomicAdd(reinterpret_cast<unsigned long long*>(s.remaining), ~0ull);   // integer: the order does not matter
+}
+
+}  // namespace
+
+// Each returns the launch status (salp_ppo.hip explains why not a later hipGetLastError()).
+extern "C" __attribute__((visibility("hidden"))) hipError_t salp_epwin_push_launch(const SalpEpisodeWindow* w,
+                                                                                    const SalpEpisodePush* p,
+                                                                                    void* stream) {
+    hipLaunchKernelGGL(k_epwin_push, dim3(1), dim3(kPushBlock), 0, (hipStream_t)stream, *w, *p);
+    return hipGetLastError();
+}
+
+extern "C" __attribute__((visibility("hidden"))) hipError_t salp_epwin_summary_launch(const SalpEpisodeWindow* w,
+                                                                                       double* out, void* stream) {
+    hipLaunchKernelGGL(k_epwin_summary, dim3(SALP_EPWIN_COLS + 2), dim3(kSumBlock), 0, (hipStream_t)stream, *w, out);
+    return hipGetLastError();
+}
+
+extern "C" __attribute__((visibility("hidden"))) hipError_t salp_eval_account_launch(const SalpEvalState* s,
+                                                                                      const SalpEpisodePush* p,
+                                                                                      void* stream) {
+    const int64_t blocks = (s->n_envs + kEvalBlock - 1) / kEvalBlock;
+    hipLaunchKernelGGL(k_eval_account, dim3((unsigned)blocks), dim3(kEvalBlock), 0, (hipStream_t)stream, *s, *p);
+    return hipGetLastError();
+}

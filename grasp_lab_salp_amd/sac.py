@@ -38,15 +38,35 @@ the critics run as the kernels of csrc/salp_sac_mlp.hip (``fused_actor``,
 
 Collection is lock-step ``salp_step`` on a stream of its own, with the
 divergence guard, episode statistics and HIP-event phase timings of
-:class:`~grasp_lab_salp_amd.ppo.PPO`.  Not built: the actor inside the chained
-simulation kernel, HIP-graph capture of the step (the kernels read what
-changes per step from device memory, so they are ready for it), several GPUs,
-callbacks, save / load.
+:class:`~grasp_lab_salp_amd.ppo.PPO`.
+
+The rest of the reference script (``src/train_robot.py:71-122``) runs too:
+``learn(callback=...)`` drives the callbacks of
+:mod:`grasp_lab_salp_amd.callbacks` after every env-step, on the collection
+stream and on the step's device tensors (``model.locals``; no list of info
+dicts is built); :meth:`SAC.evaluate` runs deterministic episodes on a second
+vector env with its bookkeeping in one launch per step
+(:class:`~grasp_lab_salp_amd.metrics.EvalAccount`); :meth:`SAC.save` /
+:meth:`SAC.load` and :meth:`SAC.save_replay_buffer` /
+:meth:`SAC.load_replay_buffer` keep everything a resumed run needs (parameters,
+targets, optimiser states, the entropy coefficient, the counters and the
+sampling generator) in a zip of this project's own layout, which is not SB3's.
+
+Not built: the actor inside the chained simulation kernel, HIP-graph capture
+of the step (the kernels read what changes per step from device memory, so
+they are ready for it), several GPUs, TensorBoard event files
+(``tensorboard_log`` is accepted and unused), rendering during evaluation, and
+reading or writing SB3's own model files.
 """
 import copy
 import ctypes
+import io
+import json
 import math
+import os
+import zipfile
 
+import numpy as np
 import torch
 from torch import nn
 
@@ -708,6 +728,7 @@ class SAC:
         if self.train_freq < 1:
             raise ValueError("train_freq must be >= 1")
         self.learning_rate, self.learning_starts = float(learning_rate), int(learning_starts)
+        self.buffer_size, self.ent_coef = int(buffer_size), ent_coef
         self.batch_size, self.tau, self.gamma = int(batch_size), float(tau), float(gamma)
         self.verbose, self.tensorboard_log, self.reset_nonfinite = verbose, tensorboard_log, bool(reset_nonfinite)
         self.seed = int(seed)
@@ -759,8 +780,17 @@ class SAC:
         self.logger = {}
         self.timing = {"collect_s": 0.0, "sample_s": 0.0, "update_s": 0.0}
         self.history = []
+        self.locals = {}               # the last env-step's device tensors, for callbacks
+        self.callback_metrics = {}     # the latest value of every key a callback recorded
+        self._recorded = {}            # ... those since the last history row
+        self.last_eval = None          # the per-episode results of the last evaluate()
+        self.predict_only = False      # SAC.load(path, env=None): no env to learn on
 
     # -------------------------------------------------------- collection
+    def _need_env(self, what):
+        if self.predict_only:
+            raise RuntimeError(f"{what}: this model was loaded without an env (SAC.load(path, env=None)): it can "
+                               "only predict; load it with env=... to train or evaluate")
     def _step_out(self):
         """Two sets of step outputs, used in turn: the observation the next
         action is taken on stays valid while the step after it is written."""
@@ -786,17 +816,44 @@ class SAC:
         mu_ls = fused_actor(self.policy.actor, obs) if self.fused_mlp else self.policy.actor(obs)
         return head(*mu_ls, eps)[0]
 
+    @torch.no_grad()
+    def _eval_action(self, obs, deterministic=True):
+        """The policy's scaled action in [-1, 1] on ``obs`` [n, obs_dim] (any
+        n): the one action function of :meth:`evaluate`.  With ``fused_mlp``
+        the actor's kernel and then the head kernel, with zero noise when
+        deterministic: fmaf(exp(ls), 0, mu) is mu for the clamped log-std, so
+        that is exactly tanh(mu).  Else the torch modules."""
+        n = obs.shape[0]
+        noise = lambda: torch.randn((n, 3), generator=self.sample_gen, device=self.device)  # noqa: E731
+        if self.fused_mlp:
+            eps = torch.zeros((n, 3), dtype=torch.float32, device=self.device) if deterministic else noise()
+            return squashed_gaussian(*fused_actor(self.policy.actor, obs), eps)[0]
+        mu, log_std = self.policy.actor(obs)
+        if deterministic:
+            return torch.tanh(mu)
+        return (squashed_gaussian if self.fused else torch_squashed_gaussian)(mu, log_std, noise())[0]
+
     def collect_step(self):
-        """One lock-step env-step of every env into the replay buffer."""
+        """One lock-step env-step of every env into the replay buffer.  The
+        step's device tensors are left in ``self.locals`` for the callbacks:
+        ``obs`` (after the step), ``actions`` (scaled to [-1, 1]), ``rewards``,
+        ``terminated``, ``truncated``, ``dones``, ``info`` [n, INFO_DIM] and
+        ``diverged`` (transitions the guard dropped).  They alias the two
+        alternating output sets of :meth:`_step_out`: the step after the next
+        overwrites them."""
+        self._need_env("collect_step")
         sim = self.sim
         if self._obs is None:
             self._obs = sim.reset()
         obs = self._obs
         a = self._sample_action(obs).contiguous()
         r = sim.step(unscale_action(a, self.low, self.high), auto_reset=True, out=self._step_out())
-        bad = self.replay.add(obs, a, r.obs, r.terminal_obs, r.reward, r.terminated, r.truncated,
-                              guard=self.reset_nonfinite).bool()
+        diverged = self.replay.add(obs, a, r.obs, r.terminal_obs, r.reward, r.terminated, r.truncated,
+                                   guard=self.reset_nonfinite)
+        bad = diverged.bool()
         done = (r.terminated | r.truncated).bool()
+        self.locals = {"obs": r.obs, "actions": a, "rewards": r.reward, "terminated": r.terminated,
+                       "truncated": r.truncated, "dones": done, "info": r.info, "diverged": diverged}
         if self.reset_nonfinite:
             # as PPO._reset_diverged: a diverged env that did not end its episode is reset on the spot
             self._nonfinite += bad.sum()
@@ -879,19 +936,31 @@ class SAC:
 
     def learn(self, total_timesteps, callback=None, tb_log_name=None, progress_bar=False, log_interval=100):
         """Collect ``train_freq`` env-steps, then train, until ``total_timesteps``
-        transitions.  ``callback``, ``tb_log_name`` and ``progress_bar`` are
-        accepted for SB3's signature and unused (callbacks are not built).
+        transitions.  ``callback``: a callback of
+        :mod:`grasp_lab_salp_amd.callbacks`, a list of them, or None;
+        ``on_training_start`` runs once, ``on_step`` after every env-step, on
+        the collection stream (which has waited for the previous update, and
+        which the update waits for: evaluation and saving see a consistent
+        policy), and ``on_training_end`` at the end.  An ``on_step`` that
+        returns False ends training after that env-step, before its update.
+        ``tb_log_name`` and ``progress_bar`` are accepted for SB3's signature
+        and unused.
         Every ``log_interval`` iterations the phase timings (HIP events: the
         collection on its stream; the first gradient step's sample and update
         on the update's stream, after it has waited for the collection, scaled
         by the number of gradient steps) and a ``history`` row are resolved;
-        that is the only host synchronisation."""
+        without callbacks that is the only host synchronisation."""
+        self._need_env("learn")
+        cb = self._as_callback(callback)
         gpu = self.device.type == "cuda"
         if gpu and self._collect_stream is None:
             self._collect_stream = torch.cuda.Stream(self.device)
         start = self.num_timesteps
         it = 0
-        while self.num_timesteps - start < total_timesteps:
+        go_on = True
+        if cb is not None:
+            cb.on_training_start({"self": self, "total_timesteps": total_timesteps}, globals())
+        while go_on and self.num_timesteps - start < total_timesteps:
             ev = None
             if gpu:
                 # the collection's eager GEMMs stay off the stream the update runs on (DESIGN.md §5 "HIP graphs")
@@ -901,13 +970,19 @@ class SAC:
                     ev = [self._event()]
                     for _ in range(self.train_freq):
                         self.collect_step()
+                        if cb is not None and not cb.on_step():
+                            go_on = False
+                            break
                     ev.append(self._event())
                 stream.wait_stream(cs)
             else:
                 for _ in range(self.train_freq):
                     self.collect_step()
+                    if cb is not None and not cb.on_step():
+                        go_on = False
+                        break
             steps = 0
-            if self.num_timesteps > self.learning_starts:
+            if go_on and self.num_timesteps > self.learning_starts:
                 steps = self.gradient_steps if self.gradient_steps >= 0 else self.train_freq * self.n_envs
                 self.train(steps, ev)
             if ev is not None:
@@ -918,7 +993,27 @@ class SAC:
                 self._log()
         if it and not logged:
             self._log()
+        if cb is not None:
+            cb.on_training_end()
         return self
+
+    def _as_callback(self, callback):
+        """None, a callback or a list of callbacks -> None or one initialised callback."""
+        if callback is None:
+            return None
+        from .callbacks import BaseCallback, CallbackList
+        if isinstance(callback, (list, tuple)):
+            callback = CallbackList(list(callback))
+        if not isinstance(callback, BaseCallback):
+            raise TypeError("callback: a grasp_lab_salp_amd.callbacks.BaseCallback, a list of them, or None")
+        callback.init_callback(self)
+        return callback
+
+    def record(self, key, value):
+        """A callback's ``logger.record``: kept in ``callback_metrics`` (latest
+        values) and added to the next ``history`` row."""
+        self.callback_metrics[key] = value
+        self._recorded[key] = value
 
     def _log(self):
         self._drain_events()
@@ -932,6 +1027,9 @@ class SAC:
                        "ep_return_mean": ret_sum / n_ep if n_ep else None,
                        "success_rate": n_succ / n_ep if n_ep else None,
                        "ep_len_mean": len_sum / n_ep if n_ep else None, "diverged_envs": self.nonfinite_resets}
+        if self._recorded:   # what callbacks recorded since the last row
+            self.logger.update(self._recorded)
+            self._recorded = {}
         self.history.append(self.logger)
         if self.verbose:
             print(self.logger, flush=True)
@@ -950,3 +1048,202 @@ class SAC:
         a = unscale_action(self.policy(obs, eps), self.low, self.high)
         a = a[0] if single else a
         return (a.cpu().numpy() if as_numpy else a), None
+
+    # ---------------------------------------------------------- evaluate
+    @torch.no_grad()
+    def evaluate(self, env, n_eval_episodes=10, deterministic=True, return_episode_rewards=False, poll_every=8):
+        """SB3 ``evaluate_policy`` on ``env`` (a :class:`SalpVecEnv` or
+        :class:`BatchedSalpEnv` of any size, on this learner's device): reset
+        it, then step all its envs in lock-step on :meth:`_eval_action`'s
+        actions until env ``i`` has finished ``(n_eval_episodes + i) // n_envs``
+        episodes.  The bookkeeping is one
+        :class:`~grasp_lab_salp_amd.metrics.EvalAccount` launch per step; the
+        number of missing episodes is copied to the host every ``poll_every``
+        steps, and the loop ends at the latest after ``max(target) *
+        max_cycles`` steps, by when every episode has timed out.  Returns
+        (mean, std) of the episode returns (``np.std``), or (returns, lengths)
+        per episode in slot order; ``last_eval`` keeps both and the successes.
+        The training env is not touched, nor ``sample_gen`` when deterministic."""
+        from .metrics import EvalAccount
+        self._need_env("evaluate")
+        sim = getattr(env, "sim", env)
+        for attr in ("step", "reset", "n_envs", "obs_dim", "params", "device"):
+            if not hasattr(sim, attr):
+                raise TypeError("evaluate: env must be a SalpVecEnv or BatchedSalpEnv, e.g. SalpVecEnv(n_eval_episodes)")
+        if int(sim.obs_dim) != self.obs_dim or torch.device(sim.device) != self.device:
+            raise ValueError(f"evaluate: env has obs_dim {sim.obs_dim} on {sim.device}; the model has {self.obs_dim} "
+                             f"on {self.device}")
+        n, od, dev = int(sim.n_envs), self.obs_dim, self.device
+        acc = EvalAccount(n_eval_episodes, n, dev, fused=self.fused)
+        out = {"obs": torch.empty((n, od), dtype=torch.float32, device=dev),
+               "reward": torch.empty(n, dtype=torch.float64, device=dev),
+               "terminated": torch.empty(n, dtype=torch.uint8, device=dev),
+               "truncated": torch.empty(n, dtype=torch.uint8, device=dev),
+               "terminal_obs": None, "info": torch.empty((n, INFO_DIM), dtype=torch.float64, device=dev)}
+        obs = sim.reset()
+        left = acc.n_eval_episodes
+        max_steps = acc.max_target * int(sim.params.max_cycles)
+        poll_every = max(int(poll_every), 1)
+        for t in range(1, max_steps + 1):
+            a = self._eval_action(obs, deterministic).contiguous()
+            r = sim.step(unscale_action(a, self.low, self.high), auto_reset=True, out=out)
+            acc.push(r.info, r.terminated, r.truncated)
+            obs = r.obs
+            if t % poll_every == 0 or t == max_steps:
+                left = acc.left()
+                if left == 0:
+                    break
+        if left:
+            raise RuntimeError(f"evaluate: {left} of {acc.n_eval_episodes} episodes did not end within {max_steps} steps")
+        returns, lengths = acc.ep_return.tolist(), [int(v) for v in acc.ep_len.tolist()]
+        self.last_eval = {"returns": returns, "lengths": lengths, "successes": [bool(s) for s in acc.success.tolist()]}
+        if return_episode_rewards:
+            return returns, lengths
+        return float(np.mean(returns)), float(np.std(returns))
+
+    # -------------------------------------------------------- save / load
+    FORMAT, FORMAT_VERSION = "grasp_lab_salp_amd.SAC", 1
+    _HYPERPARAMETERS = ("learning_rate", "buffer_size", "learning_starts", "batch_size", "tau", "gamma", "train_freq",
+                        "gradient_steps", "ent_coef", "target_entropy", "reset_nonfinite")
+
+    @staticmethod
+    def _zip_path(path):
+        path = os.fspath(path)
+        return path if os.path.splitext(path)[1] else path + ".zip"
+
+    def save(self, path):
+        """Everything a resumed run needs, as a zip of this project's own
+        layout (``.zip`` is appended to a ``path`` without a suffix; SB3 cannot
+        read it, nor this SB3's files): ``data.json`` (format tag and version,
+        hyperparameters, counters, seed, obs_dim, fused, fused_mlp),
+        ``policy.pth`` (actor, critics, target critics), ``actor.optimizer.pth``,
+        ``critic.optimizer.pth``, ``ent_coef_optimizer.pth``,
+        ``pytorch_variables.pth`` (``log_ent_coef``) and ``rng.pth`` (the state
+        of ``sample_gen``).  The replay buffer is saved apart
+        (:meth:`save_replay_buffer`).  Returns the file's path; synchronises."""
+        path = self._zip_path(path)
+        cpu = lambda t: t.detach().to("cpu", copy=True)  # noqa: E731
+
+        def opt_state(opt):
+            if opt is None:
+                return {}
+            sd = opt.state_dict()
+            return {"state": {k: {n: (cpu(v) if torch.is_tensor(v) else v) for n, v in s.items()}
+                              for k, s in sd["state"].items()}, "param_groups": sd["param_groups"]}
+
+        data = {"format": self.FORMAT, "version": self.FORMAT_VERSION,
+                "hyperparameters": {k: getattr(self, k) for k in self._HYPERPARAMETERS},
+                "num_timesteps": int(self.num_timesteps), "n_updates": int(self.n_updates),
+                "update": int(self._update), "seed": self.seed, "obs_dim": self.obs_dim, "fused": self.fused,
+                "fused_mlp": self.fused_mlp, "device_type": self.device.type}
+        files = {"policy.pth": {k: cpu(v) for k, v in self.policy.state_dict().items()},
+                 "actor.optimizer.pth": opt_state(self.actor_opt), "critic.optimizer.pth": opt_state(self.critic_opt),
+                 "ent_coef_optimizer.pth": opt_state(self.ent_coef_opt),
+                 "pytorch_variables.pth": {"log_ent_coef": cpu(self.log_ent_coef)},
+                 "rng.pth": {"sample_gen": self.sample_gen.get_state().clone()}}
+        d = os.path.dirname(path)
+        if d:
+            os.makedirs(d, exist_ok=True)
+        with zipfile.ZipFile(path, "w", zipfile.ZIP_STORED) as z:
+            z.writestr("data.json", json.dumps(data, indent=1))
+            for name, obj in files.items():
+                buf = io.BytesIO()
+                torch.save(obj, buf)
+                z.writestr(name, buf.getvalue())
+        return path
+
+    @classmethod
+    def load(cls, path, env=None, device="auto", **kwargs):
+        """A learner from :meth:`save`'s file (``.zip`` appended as there).
+        ``kwargs`` override the saved hyperparameters, as in SB3.  Tensors are
+        read with ``torch.load(weights_only=True)`` and copied into the new
+        learner's flat parameter buffers, which the kernels' raw pointers stay
+        valid for.  ``env=None`` gives a predict-only model on ``device``
+        (``"cpu"`` too; ``"auto"``: the GPU if there is one): ``predict``
+        works; ``learn``, ``collect_step`` and ``evaluate`` raise."""
+        path = cls._zip_path(path)
+        with zipfile.ZipFile(path) as z:
+            data = json.loads(z.read("data.json"))
+            if data.get("format") != cls.FORMAT or data.get("version") != cls.FORMAT_VERSION:
+                raise ValueError(f"{path}: not a {cls.FORMAT} file of version {cls.FORMAT_VERSION} "
+                                 f"(format {data.get('format')!r}, version {data.get('version')!r})")
+            blobs = {n: torch.load(io.BytesIO(z.read(n)), map_location="cpu", weights_only=True)
+                     for n in ("policy.pth", "actor.optimizer.pth", "critic.optimizer.pth", "ent_coef_optimizer.pth",
+                               "pytorch_variables.pth", "rng.pth")}
+        hp = dict(data["hyperparameters"])
+        if isinstance(hp.get("train_freq"), list):
+            hp["train_freq"] = tuple(hp["train_freq"])
+        predict_only = env is None
+        if predict_only:
+            if device in (None, "auto"):
+                device = "cuda" if torch.cuda.is_available() else "cpu"
+            env = _NoEnv(data["obs_dim"], device)
+            hp["buffer_size"] = 1                   # no replay buffer to speak of
+            device = None
+        dev_type = torch.device(getattr(env, "sim", env).device).type
+        for k, saved in (("fused", data["fused"]), ("fused_mlp", data["fused_mlp"])):
+            hp[k] = bool(saved) and dev_type == "cuda"      # the HIP kernels need the GPU they were saved on
+        hp["seed"] = data["seed"]
+        hp.update(kwargs)
+        m = cls("MlpPolicy", env, device=device, **hp)
+        if m.obs_dim != data["obs_dim"]:
+            raise ValueError(f"{path}: saved with obs_dim {data['obs_dim']}, the env has {m.obs_dim}")
+        m.predict_only = predict_only
+        if predict_only:
+            m.env = None
+        m.policy.load_state_dict(blobs["policy.pth"], strict=True)      # in place: the flat buffers stay
+        pol = m.policy
+        if not (pol.actor.is_flat() and pol.critic.is_flat() and pol.critic_target.is_flat()):
+            raise RuntimeError("SAC.load: the parameters left their flat buffers")
+        for opt, name in ((m.actor_opt, "actor.optimizer.pth"), (m.critic_opt, "critic.optimizer.pth"),
+                          (m.ent_coef_opt, "ent_coef_optimizer.pth")):
+            if opt is not None and blobs[name]:
+                groups = opt.state_dict()["param_groups"]   # this learner's own settings (lr may be overridden)
+                opt.load_state_dict({"state": blobs[name]["state"], "param_groups": groups})
+        with torch.no_grad():
+            m.log_ent_coef.copy_(blobs["pytorch_variables.pth"]["log_ent_coef"])
+        m._update.fill_(int(data["update"]))
+        m.num_timesteps, m.n_updates = int(data["num_timesteps"]), int(data["n_updates"])
+        m.logger = {"timesteps": m.num_timesteps, "n_updates": m.n_updates}
+        if data.get("device_type") == m.device.type:         # a generator's state is its device type's own
+            m.sample_gen.set_state(blobs["rng.pth"]["sample_gen"])
+        return m
+
+    def save_replay_buffer(self, path):
+        """The replay rings, the per-env cursors and the sampler's seed to ``path`` (one ``torch.save`` file)."""
+        rb = self.replay
+        d = os.path.dirname(os.fspath(path))
+        if d:
+            os.makedirs(d, exist_ok=True)
+        obj = {k: getattr(rb, k).detach().to("cpu", copy=True) for k in _REPLAY_TENSORS}
+        obj.update(capacity=rb.capacity, n_envs=rb.n_envs, obs_dim=rb.obs_dim, seed=rb.seed)
+        torch.save(obj, os.fspath(path))
+        return os.fspath(path)
+
+    def load_replay_buffer(self, path):
+        """:meth:`save_replay_buffer`'s file into this learner's rings, in
+        place (the kernels hold their raw pointers).  A file of another
+        capacity, n_envs or obs_dim raises ValueError."""
+        obj = torch.load(os.fspath(path), map_location="cpu", weights_only=True)
+        rb = self.replay
+        for k in ("capacity", "n_envs", "obs_dim"):
+            if int(obj[k]) != getattr(rb, k):
+                raise ValueError(f"{path}: replay buffer with {k} = {obj[k]}, this learner's has {getattr(rb, k)}")
+        for k in _REPLAY_TENSORS:
+            getattr(rb, k).copy_(obj[k])
+        rb.seed = int(obj["seed"])
+
+
+_REPLAY_TENSORS = ("obs", "next_obs", "actions", "rewards", "dones", "pos", "size")
+
+
+class _NoEnv:
+    """What SAC's constructor reads of an env, for a predict-only model."""
+
+    n_envs = 1
+
+    def __init__(self, obs_dim, device):
+        self.obs_dim = int(obs_dim)
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())

@@ -632,6 +632,73 @@ typedef struct SalpSacNetBackward {
 int64_t salp_sac_net_workspace_floats(int64_t batch, int d0, int d1, int out_dim, int n_nets);
 int salp_sac_net_backward(const SalpSacNetBackward* b, void* stream);
 
+/* ------------------------------------------------ Episode metrics and evaluation
+ * (csrc/salp_metrics.hip; recognised by their symbols, the ABI number stays.)
+ * The per-env-step work of the reference's training callbacks
+ * (src/train_robot.py:71-122) without a host copy: all three enqueue on the
+ * caller's stream, allocate nothing, never touch the host and use no
+ * floating-point atomic, so two runs on the same inputs give the same bits.
+ *
+ * Episode window: the device form of src/tensorboard_callback.py:36-61's
+ * deque(maxlen=100) per metric.  Episode e (0-based, counted since creation in
+ * count[0]) lives in row e % window.  Row layout:
+ *   0 ep_return   1 ep_len   2 success = terminated != 0 (only reaching the
+ *   target terminates: the reference's "terminated and not TimeLimit.truncated")
+ *   3 truncation = truncated != 0 && terminated == 0
+ *   4 .. 19  info columns SALP_INFO_PATH_LENGTH .. SALP_INFO_AVG_R_OBSTACLE in
+ *            enum order, copied bit for bit. */
+#define SALP_EPWIN_COLS 20
+#define SALP_EPWIN_MAX_WINDOW 1024
+#define SALP_EPSUM_DIM 84
+typedef struct SalpEpisodeWindow {
+    int32_t window;          /* 1 .. SALP_EPWIN_MAX_WINDOW */
+    int32_t reserved;
+    double* rows;            /* [window][SALP_EPWIN_COLS] */
+    int64_t* count;          /* [1] episodes pushed since creation */
+} SalpEpisodeWindow;
+/* One lock-step env-step as salp_step wrote it. */
+typedef struct SalpEpisodePush {
+    int64_t n_envs;
+    const double* info;          /* [n_envs][SALP_INFO_DIM] */
+    const uint8_t* terminated;   /* [n_envs] */
+    const uint8_t* truncated;    /* [n_envs] */
+    const uint8_t* skip;         /* [n_envs] or NULL */
+} SalpEpisodePush;
+/* An env finishes when (terminated | truncated) != 0 and its skip byte, if
+ * given, is 0 (the learner passes its diverged mask: a dropped transition logs
+ * no episode).  Finishers are appended in ascending env index (the reference's
+ * `for idx, info in enumerate(infos)`): with D finishers the r-th (0-based)
+ * becomes episode count + r, then count += D.  If D > window only the last
+ * `window` of them are written, so no two finishers of a push write one row.
+ * One workgroup; any n_envs >= 1. */
+int salp_episode_window_push(const SalpEpisodeWindow* w, const SalpEpisodePush* p, void* stream);
+/* What src/tensorboard_callback.py:131-205 computes.  out [SALP_EPSUM_DIM]:
+ *   out[0] = n = min(count, window)
+ *   out[1 + 4 c + {0, 1, 2, 3}] = mean, population standard deviation (two-pass,
+ *            as np.std), min, max of column c over the n rows
+ *   out[81] = mean(path_length / ep_len)   out[82] = mean ep_len over success
+ *   rows (NaN if none)   out[83] = number of success rows
+ * With n = 0, out[0] = 0 and the rest is NaN.  fp64 sums in one fixed order. */
+int salp_episode_window_summary(const SalpEpisodeWindow* w, double* out, void* stream);
+/* stable_baselines3 evaluate_policy's bookkeeping over a vector env: env i
+ * contributes target[i] = (n_eval_episodes + i) / n_envs episodes
+ * (episode_count_targets), into slots offset[i] .. (offset the exclusive prefix
+ * of target).  An env that finishes (terminated | truncated; skip is ignored)
+ * with done_count[i] < target[i] writes slot offset[i] + done_count[i],
+ * increments its count and decrements remaining[0] (an integer atomic); its
+ * later episodes are ignored. */
+typedef struct SalpEvalState {
+    int64_t n_envs;
+    const int32_t* target;   /* [n_envs] */
+    const int64_t* offset;   /* [n_envs] */
+    int32_t* done_count;     /* [n_envs] */
+    double* ep_return;       /* [n_eval_episodes] */
+    double* ep_len;          /* [n_eval_episodes] */
+    uint8_t* success;        /* [n_eval_episodes] */
+    int64_t* remaining;      /* [1] starts at n_eval_episodes */
+} SalpEvalState;
+int salp_eval_account(const SalpEvalState* s, const SalpEpisodePush* p, void* stream);
+
 /* ------------------------------------------------ Robot / Nozzle level */
 /* The reference's Robot API for callers that drive the robot directly,
  * without the task env (src/compare_trajectories.py:120-168,

@@ -233,6 +233,33 @@ static void abi_host_paths(void) {
         nbk.batch = 4; nbk.d0 = 10; nbk.d1 = 3; nbk.out_dim = 1; nbk.n_nets = 2;
         CHECK(salp_sac_net_backward(&nbk, NULL) == SALP_EINVAL && salp_sac_net_backward(NULL, NULL) == SALP_EINVAL);
     }
+    {   /* episode metrics and evaluation: argument checks (no GPU) */
+        double rows[SALP_EPWIN_COLS], out[SALP_EPSUM_DIM], info[SALP_INFO_DIM];
+        int64_t count = 0;
+        uint8_t flag = 0;
+        SalpEpisodeWindow w = {1, 0, rows, &count};
+        SalpEpisodePush ps = {1, info, &flag, &flag, NULL};
+        SalpEvalState es;
+        memset(&es, 0, sizeof es);
+        CHECK(salp_episode_window_push(NULL, &ps, NULL) == SALP_EINVAL);
+        CHECK(salp_episode_window_push(&w, NULL, NULL) == SALP_EINVAL);
+        CHECK(salp_episode_window_summary(&w, NULL, NULL) == SALP_EINVAL);
+        w.window = SALP_EPWIN_MAX_WINDOW + 1;
+        CHECK(salp_episode_window_push(&w, &ps, NULL) == SALP_EINVAL);
+        CHECK(salp_episode_window_summary(&w, out, NULL) == SALP_EINVAL);
+        w.window = 0;
+        CHECK(salp_episode_window_push(&w, &ps, NULL) == SALP_EINVAL);
+        w.window = 1;
+        ps.n_envs = 0;
+        CHECK(salp_episode_window_push(&w, &ps, NULL) == SALP_EINVAL);
+        ps.n_envs = 1;
+        ps.info = NULL;
+        CHECK(salp_episode_window_push(&w, &ps, NULL) == SALP_EINVAL);
+        ps.info = info;
+        CHECK(salp_eval_account(&es, &ps, NULL) == SALP_EINVAL && salp_eval_account(NULL, &ps, NULL) == SALP_EINVAL);
+        es.n_envs = 1;
+        CHECK(salp_eval_account(&es, &ps, NULL) == SALP_EINVAL);   /* null state buffers */
+    }
 }
 
 #ifdef SALP_SAN_GPU

@@ -25,6 +25,11 @@
 
 #include <cstdint>
 
+#include "salp_host.h"
+
+using salp::check_hip;
+using salp::fail;
+
 #pragma clang fp contract(off)
 
 namespace {
@@ -88,11 +93,13 @@ __global__ __launch_bounds__(kGaeBlock) void k_gae(int64_t T, int64_t n, const f
 
 }  // namespace
 
-// Returns the launch status; the caller reports it (salp_kernels.hip).
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_gae_launch(int64_t n_steps, int64_t n_envs, const float* rewards, const float* values,
-                               const float* episode_starts, const float* last_values,
-                               const float* last_dones, double gamma, double gae_lambda, float* advantages,
-                               float* returns, void* stream) {
+extern "C" int salp_gae(int64_t n_steps, int64_t n_envs, const float* rewards, const float* values,
+                        const float* episode_starts, const float* last_values, const float* last_dones, double gamma,
+                        double gae_lambda, float* advantages, float* returns, void* stream) {
+    if (n_steps < 0 || n_envs < 0) return fail(SALP_EINVAL, "salp_gae: negative size");
+    if (!rewards || !values || !episode_starts || !last_values || !last_dones || !advantages || !returns)
+        return fail(SALP_EINVAL, "salp_gae: null buffer");
+    if (n_steps == 0 || n_envs == 0) return SALP_OK;
     // NumPy 2: python float * float32 array -> the float is cast to float32;
     // gamma * gae_lambda is a python (double) product first.
     const float g = (float)gamma;
@@ -106,5 +113,5 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t salp_gae_launch(int6
     const unsigned blocks = (unsigned)((n_envs + bs - 1) / bs);
     hipLaunchKernelGGL(k_gae, dim3(blocks), dim3((unsigned)bs), 0, (hipStream_t)stream, n_steps, n_envs, rewards,
                        values, episode_starts, last_values, last_dones, g, gl, advantages, returns);
-    return hipGetLastError();
+    return check_hip(hipGetLastError(), "k_gae");
 }

@@ -1,4 +1,6 @@
-// salp_kernels.hip — HIP kernels for gfx950 + the C ABI of include/salp.h.
+// salp_kernels.hip — the simulator: its HIP kernels for gfx950 and its part of
+// the C ABI of include/salp.h (salp_create ... salp_state_ptr; each learner's
+// entry points are in the unit that defines its kernels).
 //
 // One env per lane, struct-of-arrays fp64 state in HBM.  Every kernel loads a
 // lane's hot state once, runs whole breathing cycles (hundreds of physics
@@ -13,7 +15,9 @@
 #include <string>
 
 #include "salp_device.h"
+#include "salp_host.h"
 #include "salp_pair.h"
+#include "salp_sort.h"
 #include "salp_tanh.h"
 
 using salp::Hot;
@@ -2373,9 +2377,11 @@ const char* const kFieldNames[SALP_NUM_FIELDS] = {
     "amt0", "amt1", "amt2", "amrt0", "amrt1", "amrt2",
     "ouf0", "ouf1", "ouf2", "out0", "out1", "out2", "rng_ctl", "rng_tick"};
 
-thread_local std::string g_last_error;
-
 }  // namespace
+
+// The one definition of salp_host.h's string: every unit's failures land here.
+__attribute__((visibility("hidden"))) thread_local std::string salp::g_last_error;
+using salp::g_last_error;
 
 struct SalpEnv {
     int device = 0;
@@ -2401,8 +2407,7 @@ namespace {
 
 int fail(SalpEnv* h, int code, const std::string& msg) {
     if (h) h->err = msg;
-    g_last_error = msg;
-    return code;
+    return salp::fail(code, msg);
 }
 
 int check_hip(SalpEnv* h, hipError_t e, const char* what) {
@@ -2414,6 +2419,14 @@ int launched(SalpEnv* h, const char* what) { return check_hip(h, hipGetLastError
 
 unsigned blocks_for(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
+// A steady budget below: its environment variable where that holds 1 .. 65535,
+// else the measured default.  Each getter reads its variable once per process.
+int32_t steady_q8_env(const char* name, int32_t measured) {
+    const char* e = std::getenv(name);
+    const long v = e ? std::strtol(e, nullptr, 10) : 0;
+    return (int32_t)(v > 0 && v < (1 << 16) ? v : measured);
+}
+
 // k_rollout's steady ticks per full tick of a wave's chunk budget (x256): a
 // steady tick costs ~0.8 of a full one in the round-2 kernel (q = 360,
 // profiles/r2_experiments.md r2l-r2o); with the fused arithmetic and settled
@@ -2422,11 +2435,7 @@ unsigned blocks_for(int64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 // profile r5f) moved it to q = 560 (480..900 swept, profiles/r5_experiments.md
 // r5g).  SALP_STEADY_Q8 overrides it for tuning runs; it changes throughput only.
 int32_t rollout_steady_q8() {
-    static const int32_t q = [] {
-        const char* e = std::getenv("SALP_STEADY_Q8");
-        const long v = e ? std::strtol(e, nullptr, 10) : 0;
-        return (int32_t)(v > 0 && v < (1 << 16) ? v : 560);
-    }();
+    static const int32_t q = steady_q8_env("SALP_STEADY_Q8", 560);
     return q;
 }
 // The same budget for k_rollout_pair, whose steady ticks cost relatively more
@@ -2436,11 +2445,7 @@ int32_t rollout_steady_q8() {
 // collect_bench at 32 768 envs 25.4 -> 26.3-26.7 M at chunk 192,
 // profiles/r5_experiments.md r5n-r5o).  SALP_PAIR_STEADY_Q8 overrides it.
 int32_t pair_steady_q8() {
-    static const int32_t q = [] {
-        const char* e = std::getenv("SALP_PAIR_STEADY_Q8");
-        const long v = e ? std::strtol(e, nullptr, 10) : 0;
-        return (int32_t)(v > 0 && v < (1 << 16) ? v : 400);
-    }();
+    static const int32_t q = steady_q8_env("SALP_PAIR_STEADY_Q8", 400);
     return q;
 }
 
@@ -2450,11 +2455,7 @@ int32_t pair_steady_q8() {
 // 16.4 M env-steps/s at round 4's 400 / 192; chunk 160-224 x q 280-440,
 // profiles/r5_experiments.md r5aa-r5ac).  SALP_PAIR_COLLECT_Q8 overrides it.
 int32_t pair_collect_steady_q8() {
-    static const int32_t q = [] {
-        const char* e = std::getenv("SALP_PAIR_COLLECT_Q8");
-        const long v = e ? std::strtol(e, nullptr, 10) : 0;
-        return (int32_t)(v > 0 && v < (1 << 16) ? v : 340);
-    }();
+    static const int32_t q = steady_q8_env("SALP_PAIR_COLLECT_Q8", 340);
     return q;
 }
 
@@ -2462,11 +2463,13 @@ int32_t pair_collect_steady_q8() {
 bool randomized(const Params& d) { return d.rand_dyn || d.rand_dist || d.rand_act || d.rand_obs || d.latency; }
 
 // The chained kernels (salp_rollout, salp_collect, chained salp_step_random):
-// k_rollout_pair (two waves per env, salp_pair.h) or k_rollout (one lane per
-// env).  Auto: the pair kernel while one env per lane would leave SIMDs
-// without a wave (n <= 64 lanes x 4 SIMDs x CUs / 2, e.g. config 5's 32 768
-// envs); SALP_ROLLOUT_KERNEL=0/1 overrides the auto choice (A/B runs).
-// The pair kernel has no randomised instance.
+// a two-wave kernel (two waves per env, salp_pair.h; use_split picks which of
+// the two) or k_rollout (one lane per env).  Auto: two waves while one env per
+// lane would leave SIMDs without a wave (n <= 64 lanes x 4 SIMDs x CUs / 2,
+// e.g. config 5's 32 768 envs); SALP_ROLLOUT_KERNEL=0/1 overrides the auto
+// choice (A/B runs): 1 selects the two-wave family, not k_rollout_pair by name
+// - that takes SALP_TWO_WAVE_KERNEL=pair as well.  The two-wave kernels have
+// no randomised instance.
 bool use_pair(const SalpEnv* h) {
     if (randomized(h->dp)) return false;
     if (h->rollout_kernel >= 0) return h->rollout_kernel >= 1;
@@ -2498,19 +2501,11 @@ bool use_split(const SalpEnv* h) {
 // profiles/r6_experiments.md r6g): q = 700 with the 176-tick chunk, PPO leg
 // 20.65 M (q 560: 20.30 M; q 900: 20.22 M).
 int32_t split_steady_q8() {
-    static const int32_t q = [] {
-        const char* e = std::getenv("SALP_SPLIT_STEADY_Q8");
-        const long v = e ? std::strtol(e, nullptr, 10) : 0;
-        return (int32_t)(v > 0 && v < (1 << 16) ? v : 560);
-    }();
+    static const int32_t q = steady_q8_env("SALP_SPLIT_STEADY_Q8", 560);
     return q;
 }
 int32_t split_collect_steady_q8() {
-    static const int32_t q = [] {
-        const char* e = std::getenv("SALP_SPLIT_COLLECT_Q8");
-        const long v = e ? std::strtol(e, nullptr, 10) : 0;
-        return (int32_t)(v > 0 && v < (1 << 16) ? v : 700);
-    }();
+    static const int32_t q = steady_q8_env("SALP_SPLIT_COLLECT_Q8", 700);
     return q;
 }
 
@@ -2593,73 +2588,6 @@ Params derive(const SalpParams& p, int64_t n, uint64_t seed, int64_t offset) {
 }
 
 }  // namespace
-
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_ppo_loss_launch(
-    int64_t B, const float* mu, const float* log_std, const float* value, const float* actions,
-    const float* old_logp, const float* adv, const float* returns, double clip_range, double ent_coef,
-    double vf_coef, int normalize_advantage, double* workspace, float* out, float* dmu, float* dvalue,
-    void* stream);
-
-extern "C" __attribute__((visibility("hidden"))) int64_t salp_ppo_mlp_params_impl(int obs_dim);
-extern "C" __attribute__((visibility("hidden"))) int64_t salp_ppo_mlp_offset_impl(int obs_dim, int tensor);
-extern "C" __attribute__((visibility("hidden"))) int64_t salp_ppo_mlp_workspace_impl(int64_t batch, int obs_dim);
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_ppo_mlp_adv_partials_launch(
-    int64_t B, int64_t n_mb, const int64_t* idx, const float* adv, double* out, void* stream);
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_ppo_mlp_grads_launch(const SalpPpoMinibatch* m,
-                                                                                       void* stream);
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_ppo_mlp_apply_launch(const SalpPpoAdam* a,
-                                                                                       void* stream);
-
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_lstm_fwd_launch(
-    int64_t m, int H, const float* G, const float* GX, const float* c_prev, const float* keep, const float* keep_next,
-    float* h, float* c, float* act, float* hk, void* stream);
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_lstm_bwd_launch(
-    int64_t m, int H, const float* act, const float* c_prev, const float* keep, const float* c, const float* dh,
-    const float* dhk_next, const float* keep_next, const float* dc, float* dG, float* dc_prev, void* stream);
-
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_sort_temp_bytes(int64_t n, size_t* bytes);
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_sort_launch(
-    void* temp, size_t temp_bytes, const uint32_t* keys_in, uint32_t* keys_out, const int32_t* ids_in,
-    int32_t* order, int64_t n, void* stream);
-
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_gae_launch(
-    int64_t n_steps, int64_t n_envs, const float* rewards, const float* values, const float* episode_starts,
-    const float* last_values, const float* last_dones, double gamma, double gae_lambda, float* advantages,
-    float* returns, void* stream);
-
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_replay_add_launch(const SalpReplay* rb,
-                                                                                    const SalpReplayAdd* a,
-                                                                                    void* stream);
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_replay_sample_launch(const SalpReplay* rb,
-                                                                                       const SalpReplaySample* s,
-                                                                                       void* stream);
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_sac_actor_fwd_launch(
-    int64_t B, const float* mu, const float* log_std, const float* eps, float* act, float* logp, void* stream);
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_sac_actor_bwd_launch(
-    int64_t B, const float* log_std, const float* eps, const float* act, const float* da, const float* dlogp,
-    float* dmu, float* dls, void* stream);
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_sac_td_launch(const SalpSacTd* t, void* stream);
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_sac_pi_launch(const SalpSacPi* p, void* stream);
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_sac_polyak_launch(int64_t n, const float* params,
-                                                                                    float* target, double tau,
-                                                                                    void* stream);
-extern "C" __attribute__((visibility("hidden"))) int salp_sac_net_tile_rows_impl(void);
-extern "C" __attribute__((visibility("hidden"))) int salp_sac_net_max_blocks_impl(void);
-extern "C" __attribute__((visibility("hidden"))) int64_t salp_sac_net_offset_impl(int in, int od, int tensor);
-extern "C" __attribute__((visibility("hidden"))) int64_t salp_sac_net_workspace_impl(int64_t B, int d0, int d1, int od,
-                                                                                     int n_nets);
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_sac_net_fwd_launch(const SalpSacNetForward* f,
-                                                                                     void* stream);
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_sac_net_bwd_launch(const SalpSacNetBackward* b,
-                                                                                     void* stream);
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_epwin_push_launch(const SalpEpisodeWindow* w,
-                                                                                    const SalpEpisodePush* p,
-                                                                                    void* stream);
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_epwin_summary_launch(const SalpEpisodeWindow* w,
-                                                                                       double* out, void* stream);
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_eval_account_launch(const SalpEvalState* s,
-                                                                                      const SalpEpisodePush* p,
-                                                                                      void* stream);
 
 extern "C" {
 
@@ -3055,289 +2983,5 @@ int salp_bench_ticks(SalpEnv* h, int32_t n_ticks, void* stream) {
 }
 
 int64_t salp_state_ptr(SalpEnv* h) { return h ? (int64_t)(intptr_t)h->state : 0; }
-
-int salp_ppo_loss(int64_t batch, const float* mu, const float* log_std, const float* value,
-                  const float* actions, const float* old_logp, const float* advantages, const float* returns,
-                  double clip_range, double ent_coef, double vf_coef, int normalize_advantage,
-                  double* workspace, float* out, float* dmu, float* dvalue, void* stream) {
-    if (batch <= 0) return fail(nullptr, SALP_EINVAL, "salp_ppo_loss: batch must be positive");
-    if (!mu || !log_std || !value || !actions || !old_logp || !advantages || !returns || !workspace || !out ||
-        !dmu || !dvalue)
-        return fail(nullptr, SALP_EINVAL, "salp_ppo_loss: null buffer");
-    if (!(clip_range >= 0)) return fail(nullptr, SALP_EINVAL, "salp_ppo_loss: clip_range must be >= 0");
-    const hipError_t e = salp_ppo_loss_launch(batch, mu, log_std, value, actions, old_logp, advantages, returns,
-                                              clip_range, ent_coef, vf_coef, normalize_advantage, workspace, out, dmu,
-                                              dvalue, stream);
-    return check_hip(nullptr, e, "k_ppo");
-}
-
-int64_t salp_ppo_mlp_num_params(int obs_dim) {
-    return (obs_dim > 0 && obs_dim <= SALP_OBS_DIM_MAX) ? salp_ppo_mlp_params_impl(obs_dim) : -1;
-}
-int64_t salp_ppo_mlp_offset(int obs_dim, int tensor) {
-    if (obs_dim <= 0 || obs_dim > SALP_OBS_DIM_MAX || tensor < 0 || tensor > SALP_MLP_N_TENSORS) return -1;
-    return salp_ppo_mlp_offset_impl(obs_dim, tensor);
-}
-int64_t salp_ppo_mlp_workspace_doubles(int64_t batch, int obs_dim) {
-    if (batch <= 0 || obs_dim <= 0 || obs_dim > SALP_OBS_DIM_MAX) return -1;
-    return salp_ppo_mlp_workspace_impl(batch, obs_dim);
-}
-
-int salp_ppo_mlp_grads(const SalpPpoMinibatch* m, void* stream) {
-    if (!m || m->batch <= 0) return fail(nullptr, SALP_EINVAL, "salp_ppo_mlp_grads: batch must be positive");
-    if (m->obs_dim <= 0 || m->obs_dim > SALP_OBS_DIM_MAX)
-        return fail(nullptr, SALP_EINVAL, "salp_ppo_mlp_grads: obs_dim out of range");
-    if (!m->idx || !m->obs || !m->actions || !m->old_log_prob || !m->advantages || !m->returns || !m->grads ||
-        !m->workspace)
-        return fail(nullptr, SALP_EINVAL, "salp_ppo_mlp_grads: null buffer");
-    for (int t = 0; t < SALP_MLP_N_TENSORS; ++t)
-        if (!m->params[t]) return fail(nullptr, SALP_EINVAL, "salp_ppo_mlp_grads: null parameter tensor");
-    if (!(m->clip_range >= 0)) return fail(nullptr, SALP_EINVAL, "salp_ppo_mlp_grads: clip_range must be >= 0");
-    return check_hip(nullptr, salp_ppo_mlp_grads_launch(m, stream), "k_mlp");
-}
-
-int salp_ppo_mlp_adv_partials(int64_t batch, int64_t n_minibatches, const int64_t* idx, const float* advantages,
-                              double* out, void* stream) {
-    if (batch <= 0 || n_minibatches <= 0 || n_minibatches > 65535)
-        return fail(nullptr, SALP_EINVAL, "salp_ppo_mlp_adv_partials: batch > 0 and 0 < n_minibatches <= 65535");
-    if (!idx || !advantages || !out) return fail(nullptr, SALP_EINVAL, "salp_ppo_mlp_adv_partials: null buffer");
-    return check_hip(nullptr, salp_ppo_mlp_adv_partials_launch(batch, n_minibatches, idx, advantages, out, stream),
-                     "k_mlp_adv_sums");
-}
-
-int salp_ppo_mlp_apply(const SalpPpoAdam* a, void* stream) {
-    if (!a || a->obs_dim <= 0 || a->obs_dim > SALP_OBS_DIM_MAX)
-        return fail(nullptr, SALP_EINVAL, "salp_ppo_mlp_apply: obs_dim out of range");
-    if (!a->grads || !a->exp_avg || !a->exp_avg_sq || !a->step)
-        return fail(nullptr, SALP_EINVAL, "salp_ppo_mlp_apply: null buffer");
-    for (int t = 0; t < SALP_MLP_N_TENSORS; ++t)
-        if (!a->params[t]) return fail(nullptr, SALP_EINVAL, "salp_ppo_mlp_apply: null parameter tensor");
-    return check_hip(nullptr, salp_ppo_mlp_apply_launch(a, stream), "k_mlp_apply");
-}
-
-int salp_lstm_cell_forward(int64_t rows, int32_t hidden, const float* gates, const float* c_prev, const float* keep,
-                           float* h, float* c, float* act, void* stream) {
-    if (rows < 0 || hidden <= 0) return fail(nullptr, SALP_EINVAL, "salp_lstm_cell_forward: bad size");
-    if (!gates || !c_prev || !keep || !h || !c || !act)
-        return fail(nullptr, SALP_EINVAL, "salp_lstm_cell_forward: null buffer");
-    if (rows == 0) return SALP_OK;
-    return check_hip(nullptr, salp_lstm_fwd_launch(rows, hidden, gates, nullptr, c_prev, keep, nullptr, h, c, act,
-                                                   nullptr, stream), "k_lstm_fwd");
-}
-
-int salp_lstm_step_forward(int64_t rows, int32_t hidden, const float* gates, const float* gx, const float* c_prev,
-                           const float* keep, const float* keep_next, float* h, float* c, float* act, float* hk_next,
-                           void* stream) {
-    if (rows < 0 || hidden <= 0) return fail(nullptr, SALP_EINVAL, "salp_lstm_step_forward: bad size");
-    if (!gates || !c_prev || !keep || !h || !c || !act)
-        return fail(nullptr, SALP_EINVAL, "salp_lstm_step_forward: null buffer");
-    if (!keep_next != !hk_next)
-        return fail(nullptr, SALP_EINVAL, "salp_lstm_step_forward: keep_next and hk_next go together");
-    if (rows == 0) return SALP_OK;
-    return check_hip(nullptr, salp_lstm_fwd_launch(rows, hidden, gates, gx, c_prev, keep, keep_next, h, c, act,
-                                                   hk_next, stream), "k_lstm_fwd");
-}
-
-int salp_lstm_cell_backward(int64_t rows, int32_t hidden, const float* act, const float* c_prev, const float* keep,
-                            const float* c, const float* dh, const float* dc, float* dgates, float* dc_prev,
-                            void* stream) {
-    if (rows < 0 || hidden <= 0) return fail(nullptr, SALP_EINVAL, "salp_lstm_cell_backward: bad size");
-    if (!act || !c_prev || !keep || !c || !dh || !dgates || !dc_prev)
-        return fail(nullptr, SALP_EINVAL, "salp_lstm_cell_backward: null buffer");
-    if (rows == 0) return SALP_OK;
-    return check_hip(nullptr, salp_lstm_bwd_launch(rows, hidden, act, c_prev, keep, c, dh, nullptr, nullptr, dc, dgates,
-                                                   dc_prev, stream), "k_lstm_bwd");
-}
-
-int salp_lstm_step_backward(int64_t rows, int32_t hidden, const float* act, const float* c_prev, const float* keep,
-                            const float* c, const float* d_out, const float* dhk_next, const float* keep_next,
-                            const float* dc, float* dgates, float* dc_prev, void* stream) {
-    if (rows < 0 || hidden <= 0) return fail(nullptr, SALP_EINVAL, "salp_lstm_step_backward: bad size");
-    if (!act || !c_prev || !keep || !c || !d_out || !dgates || !dc_prev)
-        return fail(nullptr, SALP_EINVAL, "salp_lstm_step_backward: null buffer");
-    if (!dhk_next != !keep_next)
-        return fail(nullptr, SALP_EINVAL, "salp_lstm_step_backward: dhk_next and keep_next go together");
-    if (rows == 0) return SALP_OK;
-    return check_hip(nullptr, salp_lstm_bwd_launch(rows, hidden, act, c_prev, keep, c, d_out, dhk_next, keep_next, dc,
-                                                   dgates, dc_prev, stream), "k_lstm_bwd");
-}
-
-int salp_gae(int64_t n_steps, int64_t n_envs, const float* rewards, const float* values,
-             const float* episode_starts, const float* last_values, const float* last_dones, double gamma,
-             double gae_lambda, float* advantages, float* returns, void* stream) {
-    if (n_steps < 0 || n_envs < 0) return fail(nullptr, SALP_EINVAL, "salp_gae: negative size");
-    if (!rewards || !values || !episode_starts || !last_values || !last_dones || !advantages || !returns)
-        return fail(nullptr, SALP_EINVAL, "salp_gae: null buffer");
-    if (n_steps == 0 || n_envs == 0) return SALP_OK;
-    const hipError_t e = salp_gae_launch(n_steps, n_envs, rewards, values, episode_starts, last_values, last_dones,
-                                         gamma, gae_lambda, advantages, returns, stream);
-    return check_hip(nullptr, e, "k_gae");
-}
-
-static bool replay_ok(const SalpReplay* rb) {
-    // row indices stay far inside int64: capacity x n_envs x obs_dim elements are allocated by the caller
-    return rb && rb->capacity > 0 && rb->n_envs > 0 && rb->obs_dim > 0 && rb->obs_dim <= SALP_OBS_DIM_MAX &&
-           rb->n_envs <= INT32_MAX && rb->obs && rb->next_obs && rb->actions && rb->rewards && rb->dones && rb->pos &&
-           rb->size;
-}
-
-int salp_replay_add(const SalpReplay* rb, const SalpReplayAdd* a, void* stream) {
-    if (!replay_ok(rb)) return fail(nullptr, SALP_EINVAL, "salp_replay_add: bad replay buffer");
-    if (!a || !a->obs || !a->actions || !a->obs_after || !a->terminal_obs || !a->reward || !a->terminated ||
-        !a->truncated)
-        return fail(nullptr, SALP_EINVAL, "salp_replay_add: null buffer");
-    return check_hip(nullptr, salp_replay_add_launch(rb, a, stream), "k_replay_add");
-}
-
-int salp_replay_sample(const SalpReplay* rb, const SalpReplaySample* s, void* stream) {
-    if (!replay_ok(rb)) return fail(nullptr, SALP_EINVAL, "salp_replay_sample: bad replay buffer");
-    if (!s || s->batch <= 0 || s->batch > (int64_t)1 << 32)   // the row index is a 32-bit Philox counter word
-        return fail(nullptr, SALP_EINVAL, "salp_replay_sample: batch must be in 1 .. 2^32");
-    if (!s->update || !s->obs || !s->next_obs || !s->actions || !s->rewards || !s->dones)
-        return fail(nullptr, SALP_EINVAL, "salp_replay_sample: null buffer");
-    return check_hip(nullptr, salp_replay_sample_launch(rb, s, stream), "k_replay_sample");
-}
-
-int salp_sac_actor_head_forward(int64_t batch, const float* mu, const float* log_std, const float* eps,
-                                float* act, float* logp, void* stream) {
-    if (batch <= 0) return fail(nullptr, SALP_EINVAL, "salp_sac_actor_head_forward: batch must be positive");
-    if (!mu || !log_std || !eps || !act || !logp)
-        return fail(nullptr, SALP_EINVAL, "salp_sac_actor_head_forward: null buffer");
-    return check_hip(nullptr, salp_sac_actor_fwd_launch(batch, mu, log_std, eps, act, logp, stream), "k_actor_fwd");
-}
-
-int salp_sac_actor_head_backward(int64_t batch, const float* log_std, const float* eps, const float* act,
-                                 const float* da, const float* dlogp, float* dmu, float* dls, void* stream) {
-    if (batch <= 0) return fail(nullptr, SALP_EINVAL, "salp_sac_actor_head_backward: batch must be positive");
-    if (!log_std || !eps || !act || !dmu || !dls)
-        return fail(nullptr, SALP_EINVAL, "salp_sac_actor_head_backward: null buffer");
-    return check_hip(nullptr, salp_sac_actor_bwd_launch(batch, log_std, eps, act, da, dlogp, dmu, dls, stream),
-                     "k_actor_bwd");
-}
-
-int salp_sac_td_head(const SalpSacTd* t, void* stream) {
-    if (!t || t->batch <= 0) return fail(nullptr, SALP_EINVAL, "salp_sac_td_head: batch must be positive");
-    if (!t->rewards || !t->dones || !t->q1_target || !t->q2_target || !t->logp_next || !t->q1 || !t->q2 || !t->logp ||
-        !t->log_alpha || !t->workspace || !t->target || !t->dq1 || !t->dq2 || !t->out || !t->alpha_used)
-        return fail(nullptr, SALP_EINVAL, "salp_sac_td_head: null buffer");
-    return check_hip(nullptr, salp_sac_td_launch(t, stream), "k_td");
-}
-
-int salp_sac_pi_head(const SalpSacPi* p, void* stream) {
-    if (!p || p->batch <= 0) return fail(nullptr, SALP_EINVAL, "salp_sac_pi_head: batch must be positive");
-    if (!p->alpha_used || !p->logp || !p->q1_pi || !p->q2_pi || !p->workspace || !p->out || !p->dlogp || !p->dq1 ||
-        !p->dq2)
-        return fail(nullptr, SALP_EINVAL, "salp_sac_pi_head: null buffer");
-    return check_hip(nullptr, salp_sac_pi_launch(p, stream), "k_pi");
-}
-
-int salp_sac_polyak(int64_t n, const float* params, float* target, double tau, void* stream) {
-    if (n <= 0 || !params || !target) return fail(nullptr, SALP_EINVAL, "salp_sac_polyak: bad argument");
-    if (!(tau >= 0 && tau <= 1)) return fail(nullptr, SALP_EINVAL, "salp_sac_polyak: tau must be in [0, 1]");
-    return check_hip(nullptr, salp_sac_polyak_launch(n, params, target, tau, stream), "k_polyak");
-}
-
-namespace {
-bool sac_net_dims_ok(int in, int od) {
-    return in >= 1 && in <= SALP_SAC_NET_IN_MAX && od >= 1 && od <= SALP_SAC_NET_OUT_MAX;
-}
-// the part SalpSacNetForward and SalpSacNetBackward share; nullptr if it is sound, else what is wrong
-const char* sac_net_bad(int64_t batch, int d0, int d1, int od, int n_nets, const float* const* params,
-                        const float* const* x0, const float* const* x1) {
-    if (batch <= 0 || batch > INT32_MAX) return "batch must be in 1 .. 2^31 - 1";
-    if (d0 < 1 || d1 < 0 || !sac_net_dims_ok(d0 + d1, od)) return "d0 >= 1, d1 >= 0, d0 + d1 <= 17 and out_dim in 1 .. 6";
-    if (n_nets < 1 || n_nets > SALP_SAC_NET_MAX_NETS) return "n_nets must be in 1 .. 4";
-    for (int i = 0; i < n_nets; ++i)
-        if (!params[i] || !x0[i] || (d1 > 0 && !x1[i])) return "null params, x0 or x1";
-    return nullptr;
-}
-}  // namespace
-
-int64_t salp_sac_net_num_params(int in_dim, int out_dim) {
-    return salp_sac_net_offset(in_dim, out_dim, SALP_SAC_NET_N_TENSORS);
-}
-
-int64_t salp_sac_net_offset(int in_dim, int out_dim, int tensor) {
-    if (!sac_net_dims_ok(in_dim, out_dim) || tensor < 0 || tensor > SALP_SAC_NET_N_TENSORS) {
-        fail(nullptr, SALP_EINVAL, "salp_sac_net_offset: in_dim in 1 .. 17, out_dim in 1 .. 6, tensor in 0 .. 6");
-        return -1;
-    }
-    return salp_sac_net_offset_impl(in_dim, out_dim, tensor);
-}
-
-int salp_sac_net_tile_rows(void) { return salp_sac_net_tile_rows_impl(); }
-int salp_sac_net_max_blocks(void) { return salp_sac_net_max_blocks_impl(); }
-
-int64_t salp_sac_net_workspace_floats(int64_t batch, int d0, int d1, int out_dim, int n_nets) {
-    if (batch <= 0 || batch > INT32_MAX || d0 < 1 || d1 < 0 || !sac_net_dims_ok(d0 + d1, out_dim) || n_nets < 1 ||
-        n_nets > SALP_SAC_NET_MAX_NETS) {
-        fail(nullptr, SALP_EINVAL, "salp_sac_net_workspace_floats: bad argument");
-        return -1;
-    }
-    return salp_sac_net_workspace_impl(batch, d0, d1, out_dim, n_nets);
-}
-
-int salp_sac_net_forward(const SalpSacNetForward* f, void* stream) {
-    if (!f) return fail(nullptr, SALP_EINVAL, "salp_sac_net_forward: null argument");
-    if (const char* bad = sac_net_bad(f->batch, f->d0, f->d1, f->out_dim, f->n_nets, f->params, f->x0, f->x1))
-        return fail(nullptr, SALP_EINVAL, std::string("salp_sac_net_forward: ") + bad);
-    for (int i = 0; i < f->n_nets; ++i) {
-        if (!f->out[i]) return fail(nullptr, SALP_EINVAL, "salp_sac_net_forward: null out");
-        if (!f->h1[i] != !f->h2[i])
-            return fail(nullptr, SALP_EINVAL, "salp_sac_net_forward: h1 and h2 are both NULL or both set");
-    }
-    return check_hip(nullptr, salp_sac_net_fwd_launch(f, stream), "k_sac_net_fwd");
-}
-
-int salp_sac_net_backward(const SalpSacNetBackward* b, void* stream) {
-    if (!b) return fail(nullptr, SALP_EINVAL, "salp_sac_net_backward: null argument");
-    if (const char* bad = sac_net_bad(b->batch, b->d0, b->d1, b->out_dim, b->n_nets, b->params, b->x0, b->x1))
-        return fail(nullptr, SALP_EINVAL, std::string("salp_sac_net_backward: ") + bad);
-    for (int i = 0; i < b->n_nets; ++i) {
-        if (!b->h1[i] || !b->h2[i] || !b->dout[i])
-            return fail(nullptr, SALP_EINVAL, "salp_sac_net_backward: null h1, h2 or dout");
-        if (!b->dparams[i] != !b->dparams[0])
-            return fail(nullptr, SALP_EINVAL, "salp_sac_net_backward: dparams are all NULL or all set");
-    }
-    if (!b->dparams[0] && !b->dx1)
-        return fail(nullptr, SALP_EINVAL, "salp_sac_net_backward: neither dparams nor dx1 is set");
-    if (b->dx1 && b->d1 == 0) return fail(nullptr, SALP_EINVAL, "salp_sac_net_backward: dx1 needs d1 > 0");
-    if (!b->workspace) return fail(nullptr, SALP_EINVAL, "salp_sac_net_backward: null workspace");
-    return check_hip(nullptr, salp_sac_net_bwd_launch(b, stream), "k_sac_net_bwd");
-}
-
-static bool epwin_ok(const SalpEpisodeWindow* w) {
-    return w && w->window >= 1 && w->window <= SALP_EPWIN_MAX_WINDOW && w->rows && w->count;
-}
-
-static bool eppush_ok(const SalpEpisodePush* p) {
-    return p && p->n_envs >= 1 && p->info && p->terminated && p->truncated;
-}
-
-int salp_episode_window_push(const SalpEpisodeWindow* w, const SalpEpisodePush* p, void* stream) {
-    if (!epwin_ok(w))
-        return fail(nullptr, SALP_EINVAL, "salp_episode_window_push: window must be in 1 .. 1024, rows and count set");
-    if (!eppush_ok(p))
-        return fail(nullptr, SALP_EINVAL, "salp_episode_window_push: n_envs >= 1 and info, terminated, truncated set");
-    return check_hip(nullptr, salp_epwin_push_launch(w, p, stream), "k_epwin_push");
-}
-
-int salp_episode_window_summary(const SalpEpisodeWindow* w, double* out, void* stream) {
-    if (!epwin_ok(w))
-        return fail(nullptr, SALP_EINVAL,
-                    "salp_episode_window_summary: window must be in 1 .. 1024, rows and count set");
-    if (!out) return fail(nullptr, SALP_EINVAL, "salp_episode_window_summary: null out");
-    return check_hip(nullptr, salp_epwin_summary_launch(w, out, stream), "k_epwin_summary");
-}
-
-int salp_eval_account(const SalpEvalState* s, const SalpEpisodePush* p, void* stream) {
-    if (!s || s->n_envs < 1 || s->n_envs > INT32_MAX * (int64_t)256)
-        return fail(nullptr, SALP_EINVAL, "salp_eval_account: n_envs must be positive");
-    if (!s->target || !s->offset || !s->done_count || !s->ep_return || !s->ep_len || !s->success || !s->remaining)
-        return fail(nullptr, SALP_EINVAL, "salp_eval_account: null state buffer");
-    if (!eppush_ok(p) || p->n_envs != s->n_envs)
-        return fail(nullptr, SALP_EINVAL, "salp_eval_account: the step must be of the state's n_envs, buffers set");
-    return check_hip(nullptr, salp_eval_account_launch(s, p, stream), "k_eval_account");
-}
 
 }  // extern "C"

@@ -16,6 +16,11 @@
 
 #include <cstdint>
 
+#include "salp_host.h"
+
+using salp::check_hip;
+using salp::fail;
+
 namespace {
 
 __device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
@@ -87,21 +92,69 @@ __global__ __launch_bounds__(256) void k_lstm_bwd(int64_t m, int H, const float*
     dc_prev[e] = dcn * fg * kp;
 }
 
-}  // namespace
-
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_lstm_fwd_launch(
-    int64_t m, int H, const float* G, const float* GX, const float* c_prev, const float* keep, const float* keep_next,
-    float* h, float* c, float* act, float* hk, void* stream) {
+// The cell and the sequence step share a kernel: the cell is the step without GX, keep_next and hk.
+int launch_fwd(int64_t m, int H, const float* G, const float* GX, const float* c_prev, const float* keep,
+               const float* keep_next, float* h, float* c, float* act, float* hk, void* stream) {
     const int64_t n = m * H;
     hipLaunchKernelGGL(k_lstm_fwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, m, H, G, GX,
                        c_prev, keep, keep_next, h, c, act, hk);
-    return hipGetLastError();
+    return check_hip(hipGetLastError(), "k_lstm_fwd");
 }
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_lstm_bwd_launch(
-    int64_t m, int H, const float* act, const float* c_prev, const float* keep, const float* c, const float* dh,
-    const float* dhk_next, const float* keep_next, const float* dc, float* dG, float* dc_prev, void* stream) {
+
+int launch_bwd(int64_t m, int H, const float* act, const float* c_prev, const float* keep, const float* c,
+               const float* dh, const float* dhk_next, const float* keep_next, const float* dc, float* dG,
+               float* dc_prev, void* stream) {
     const int64_t n = m * H;
     hipLaunchKernelGGL(k_lstm_bwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, m, H,
                        act, c_prev, keep, c, dh, dhk_next, keep_next, dc, dG, dc_prev);
-    return hipGetLastError();
+    return check_hip(hipGetLastError(), "k_lstm_bwd");
 }
+
+}  // namespace
+
+extern "C" {
+
+int salp_lstm_cell_forward(int64_t rows, int32_t hidden, const float* gates, const float* c_prev, const float* keep,
+                           float* h, float* c, float* act, void* stream) {
+    if (rows < 0 || hidden <= 0) return fail(SALP_EINVAL, "salp_lstm_cell_forward: bad size");
+    if (!gates || !c_prev || !keep || !h || !c || !act)
+        return fail(SALP_EINVAL, "salp_lstm_cell_forward: null buffer");
+    if (rows == 0) return SALP_OK;
+    return launch_fwd(rows, hidden, gates, nullptr, c_prev, keep, nullptr, h, c, act, nullptr, stream);
+}
+
+int salp_lstm_step_forward(int64_t rows, int32_t hidden, const float* gates, const float* gx, const float* c_prev,
+                           const float* keep, const float* keep_next, float* h, float* c, float* act, float* hk_next,
+                           void* stream) {
+    if (rows < 0 || hidden <= 0) return fail(SALP_EINVAL, "salp_lstm_step_forward: bad size");
+    if (!gates || !c_prev || !keep || !h || !c || !act)
+        return fail(SALP_EINVAL, "salp_lstm_step_forward: null buffer");
+    if (!keep_next != !hk_next)
+        return fail(SALP_EINVAL, "salp_lstm_step_forward: keep_next and hk_next go together");
+    if (rows == 0) return SALP_OK;
+    return launch_fwd(rows, hidden, gates, gx, c_prev, keep, keep_next, h, c, act, hk_next, stream);
+}
+
+int salp_lstm_cell_backward(int64_t rows, int32_t hidden, const float* act, const float* c_prev, const float* keep,
+                            const float* c, const float* dh, const float* dc, float* dgates, float* dc_prev,
+                            void* stream) {
+    if (rows < 0 || hidden <= 0) return fail(SALP_EINVAL, "salp_lstm_cell_backward: bad size");
+    if (!act || !c_prev || !keep || !c || !dh || !dgates || !dc_prev)
+        return fail(SALP_EINVAL, "salp_lstm_cell_backward: null buffer");
+    if (rows == 0) return SALP_OK;
+    return launch_bwd(rows, hidden, act, c_prev, keep, c, dh, nullptr, nullptr, dc, dgates, dc_prev, stream);
+}
+
+int salp_lstm_step_backward(int64_t rows, int32_t hidden, const float* act, const float* c_prev, const float* keep,
+                            const float* c, const float* d_out, const float* dhk_next, const float* keep_next,
+                            const float* dc, float* dgates, float* dc_prev, void* stream) {
+    if (rows < 0 || hidden <= 0) return fail(SALP_EINVAL, "salp_lstm_step_backward: bad size");
+    if (!act || !c_prev || !keep || !c || !d_out || !dgates || !dc_prev)
+        return fail(SALP_EINVAL, "salp_lstm_step_backward: null buffer");
+    if (!dhk_next != !keep_next)
+        return fail(SALP_EINVAL, "salp_lstm_step_backward: dhk_next and keep_next go together");
+    if (rows == 0) return SALP_OK;
+    return launch_bwd(rows, hidden, act, c_prev, keep, c, d_out, dhk_next, keep_next, dc, dgates, dc_prev, stream);
+}
+
+}  // extern "C"

@@ -21,6 +21,10 @@
 #include <cstdint>
 
 #include "../../include/salp.h"
+#include "salp_host.h"
+
+using salp::check_hip;
+using salp::fail;
 
 namespace {
 
@@ -191,26 +195,47 @@ __global__ __launch_bounds__(kEvalBlock) void k_eval_account(SalpEvalState s, Sa
     atomicAdd(reinterpret_cast<unsigned long long*>(s.remaining), ~0ull);   // integer: the order does not matter
 }
 
+bool epwin_ok(const SalpEpisodeWindow* w) {
+    return w && w->window >= 1 && w->window <= SALP_EPWIN_MAX_WINDOW && w->rows && w->count;
+}
+
+bool eppush_ok(const SalpEpisodePush* p) {
+    return p && p->n_envs >= 1 && p->info && p->terminated && p->truncated;
+}
+
 }  // namespace
 
-// Each returns the launch status (salp_ppo.hip explains why not a later hipGetLastError()).
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_epwin_push_launch(const SalpEpisodeWindow* w,
-                                                                                    const SalpEpisodePush* p,
-                                                                                    void* stream) {
+extern "C" {
+
+// The launch status of each: one hipGetLastError() right after the launch (salp_ppo.hip explains why).
+int salp_episode_window_push(const SalpEpisodeWindow* w, const SalpEpisodePush* p, void* stream) {
+    if (!epwin_ok(w))
+        return fail(SALP_EINVAL, "salp_episode_window_push: window must be in 1 .. 1024, rows and count set");
+    if (!eppush_ok(p))
+        return fail(SALP_EINVAL, "salp_episode_window_push: n_envs >= 1 and info, terminated, truncated set");
     hipLaunchKernelGGL(k_epwin_push, dim3(1), dim3(kPushBlock), 0, (hipStream_t)stream, *w, *p);
-    return hipGetLastError();
+    return check_hip(hipGetLastError(), "k_epwin_push");
 }
 
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_epwin_summary_launch(const SalpEpisodeWindow* w,
-                                                                                       double* out, void* stream) {
+int salp_episode_window_summary(const SalpEpisodeWindow* w, double* out, void* stream) {
+    if (!epwin_ok(w))
+        return fail(SALP_EINVAL, "salp_episode_window_summary: window must be in 1 .. 1024, rows and count set");
+    if (!out) return fail(SALP_EINVAL, "salp_episode_window_summary: null out");
     hipLaunchKernelGGL(k_epwin_summary, dim3(SALP_EPWIN_COLS + 2), dim3(kSumBlock), 0, (hipStream_t)stream, *w, out);
-    return hipGetLastError();
+    return check_hip(hipGetLastError(), "k_epwin_summary");
 }
 
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_eval_account_launch(const SalpEvalState* s,
-                                                                                      const SalpEpisodePush* p,
-                                                                                      void* stream) {
+int salp_eval_account(const SalpEvalState* s, const SalpEpisodePush* p, void* stream) {
+    static_assert(kEvalBlock == 256, "the bound below is INT32_MAX blocks of kEvalBlock envs");
+    if (!s || s->n_envs < 1 || s->n_envs > INT32_MAX * (int64_t)256)
+        return fail(SALP_EINVAL, "salp_eval_account: n_envs must be positive");
+    if (!s->target || !s->offset || !s->done_count || !s->ep_return || !s->ep_len || !s->success || !s->remaining)
+        return fail(SALP_EINVAL, "salp_eval_account: null state buffer");
+    if (!eppush_ok(p) || p->n_envs != s->n_envs)
+        return fail(SALP_EINVAL, "salp_eval_account: the step must be of the state's n_envs, buffers set");
     const int64_t blocks = (s->n_envs + kEvalBlock - 1) / kEvalBlock;
     hipLaunchKernelGGL(k_eval_account, dim3((unsigned)blocks), dim3(kEvalBlock), 0, (hipStream_t)stream, *s, *p);
-    return hipGetLastError();
+    return check_hip(hipGetLastError(), "k_eval_account");
 }
+
+}  // extern "C"

@@ -29,6 +29,11 @@
 #include <cmath>
 #include <cstdint>
 
+#include "salp_host.h"
+
+using salp::check_hip;
+using salp::fail;
+
 namespace {
 
 constexpr int kPpoBlock = 256;
@@ -155,22 +160,28 @@ static_assert(kPpoGrid <= kPpoBlock, "k_ppo_final reduces one partial per thread
 
 }  // namespace
 
-// Returns the launch status (hipSuccess or the error the launches left); the
-// caller builds its message from this value, not from a second
-// hipGetLastError() (which would read the already-cleared error).
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_ppo_loss_launch(
-    int64_t B, const float* mu, const float* log_std, const float* value, const float* actions,
-    const float* old_logp, const float* adv, const float* returns, double clip_range, double ent_coef,
-    double vf_coef, int normalize_advantage, double* workspace, float* out, float* dmu, float* dvalue,
-    void* stream) {
+// The launch status (hipSuccess or the error the launches left) is read by one
+// hipGetLastError() right after them and the message is built from that value:
+// a second hipGetLastError() would read the already-cleared error.  Every
+// entry point of the library reports its launches this way.
+extern "C" int salp_ppo_loss(int64_t batch, const float* mu, const float* log_std, const float* value,
+                             const float* actions, const float* old_logp, const float* advantages,
+                             const float* returns, double clip_range, double ent_coef, double vf_coef,
+                             int normalize_advantage, double* workspace, float* out, float* dmu, float* dvalue,
+                             void* stream) {
+    if (batch <= 0) return fail(SALP_EINVAL, "salp_ppo_loss: batch must be positive");
+    if (!mu || !log_std || !value || !actions || !old_logp || !advantages || !returns || !workspace || !out ||
+        !dmu || !dvalue)
+        return fail(SALP_EINVAL, "salp_ppo_loss: null buffer");
+    if (!(clip_range >= 0)) return fail(SALP_EINVAL, "salp_ppo_loss: clip_range must be >= 0");
     hipStream_t s = (hipStream_t)stream;
     double* adv_part = workspace;
     double* row_part = workspace + 2 * kPpoGrid;
-    hipLaunchKernelGGL(k_ppo_adv_sums, dim3(kPpoGrid), dim3(kPpoBlock), 0, s, B, adv, adv_part);
-    hipLaunchKernelGGL(k_ppo_rows, dim3(kPpoGrid), dim3(kPpoBlock), 0, s, B, mu, log_std, value, actions, old_logp,
-                       adv, returns, (float)clip_range, (float)vf_coef, normalize_advantage, adv_part, row_part, dmu,
-                       dvalue);
-    hipLaunchKernelGGL(k_ppo_final, dim3(1), dim3(kPpoBlock), 0, s, B, log_std, (float)ent_coef, (float)vf_coef,
+    hipLaunchKernelGGL(k_ppo_adv_sums, dim3(kPpoGrid), dim3(kPpoBlock), 0, s, batch, advantages, adv_part);
+    hipLaunchKernelGGL(k_ppo_rows, dim3(kPpoGrid), dim3(kPpoBlock), 0, s, batch, mu, log_std, value, actions,
+                       old_logp, advantages, returns, (float)clip_range, (float)vf_coef, normalize_advantage, adv_part,
+                       row_part, dmu, dvalue);
+    hipLaunchKernelGGL(k_ppo_final, dim3(1), dim3(kPpoBlock), 0, s, batch, log_std, (float)ent_coef, (float)vf_coef,
                        row_part, out);
-    return hipGetLastError();
+    return check_hip(hipGetLastError(), "k_ppo");
 }

@@ -41,7 +41,11 @@
 #include <cstdint>
 
 #include "../../include/salp.h"
+#include "salp_host.h"
 #include "salp_tanh.h"
+
+using salp::check_hip;
+using salp::fail;
 
 namespace {
 
@@ -794,31 +798,46 @@ __global__ __launch_bounds__(NT_ADAM) void k_mlp_adam(SalpPpoAdam o, Layout L, f
     }
 }
 
-}  // namespace
-
-extern "C" __attribute__((visibility("hidden"))) int64_t salp_ppo_mlp_params_impl(int obs_dim) {
-    return make_layout(obs_dim).off[SALP_MLP_N_TENSORS];
-}
-extern "C" __attribute__((visibility("hidden"))) int64_t salp_ppo_mlp_offset_impl(int obs_dim, int tensor) {
-    return make_layout(obs_dim).off[tensor];
-}
+bool obs_dim_ok(int obs_dim) { return obs_dim > 0 && obs_dim <= SALP_OBS_DIM_MAX; }
 
 // Blocks of the row kernel and the workspace they need (doubles).
-static int row_blocks(int64_t B) {
+int row_blocks(int64_t B) {
     const int64_t tiles = (B + TR - 1) / TR;
     return (int)(tiles < NB_MAX ? tiles : NB_MAX);
 }
-extern "C" __attribute__((visibility("hidden"))) int64_t salp_ppo_mlp_workspace_impl(int64_t B, int obs_dim) {
-    const int nb = row_blocks(B);
+
+}  // namespace
+
+extern "C" {
+
+int64_t salp_ppo_mlp_num_params(int obs_dim) {
+    return obs_dim_ok(obs_dim) ? make_layout(obs_dim).off[SALP_MLP_N_TENSORS] : -1;
+}
+
+int64_t salp_ppo_mlp_offset(int obs_dim, int tensor) {
+    if (!obs_dim_ok(obs_dim) || tensor < 0 || tensor > SALP_MLP_N_TENSORS) return -1;
+    return make_layout(obs_dim).off[tensor];
+}
+
+int64_t salp_ppo_mlp_workspace_doubles(int64_t batch, int obs_dim) {
+    if (batch <= 0 || !obs_dim_ok(obs_dim)) return -1;
+    const int nb = row_blocks(batch);
     const int64_t P = make_layout(obs_dim).off[SALP_MLP_N_TENSORS];
     // adv partials, stats partials (doubles) + fp32 parameter partials (as doubles, rounded up)
     return 2 * NADV + (int64_t)nb * NSTAT + ((int64_t)nb * P + 1) / 2;
 }
 
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_ppo_mlp_grads_launch(const SalpPpoMinibatch* mb,
-                                                                                       void* stream) {
-    hipStream_t s = (hipStream_t)stream;
+// The launch status of each: one hipGetLastError() right after the launches (salp_ppo.hip explains why).
+int salp_ppo_mlp_grads(const SalpPpoMinibatch* mb, void* stream) {
+    if (!mb || mb->batch <= 0) return fail(SALP_EINVAL, "salp_ppo_mlp_grads: batch must be positive");
     const SalpPpoMinibatch& m = *mb;
+    if (!obs_dim_ok(m.obs_dim)) return fail(SALP_EINVAL, "salp_ppo_mlp_grads: obs_dim out of range");
+    if (!m.idx || !m.obs || !m.actions || !m.old_log_prob || !m.advantages || !m.returns || !m.grads || !m.workspace)
+        return fail(SALP_EINVAL, "salp_ppo_mlp_grads: null buffer");
+    for (int t = 0; t < SALP_MLP_N_TENSORS; ++t)
+        if (!m.params[t]) return fail(SALP_EINVAL, "salp_ppo_mlp_grads: null parameter tensor");
+    if (!(m.clip_range >= 0)) return fail(SALP_EINVAL, "salp_ppo_mlp_grads: clip_range must be >= 0");
+    hipStream_t s = (hipStream_t)stream;
     const int nb = row_blocks(m.batch);
     const Layout L = make_layout(m.obs_dim);
     double* const ws_adv = m.workspace;
@@ -835,19 +854,27 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t salp_ppo_mlp_grads_l
     hipLaunchKernelGGL(k_mlp_fwd_bwd, dim3(nb), dim3(NT), 0, s, a);
     const int64_t P = L.off[SALP_MLP_N_TENSORS];
     hipLaunchKernelGGL(k_mlp_reduce, dim3((unsigned)((P + 63) / 64)), dim3(NT_RED), 0, s, m, L, nb, part, stat_part);
-    return hipGetLastError();
+    return check_hip(hipGetLastError(), "k_mlp");
 }
 
 static_assert(2 * NADV == SALP_PPO_ADV_PARTIAL_DOUBLES, "include/salp.h advantage partials per minibatch");
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_ppo_mlp_adv_partials_launch(
-        int64_t B, int64_t n_mb, const int64_t* idx, const float* adv, double* out, void* stream) {
-    hipLaunchKernelGGL(k_mlp_adv_sums, dim3(NADV, (unsigned)n_mb), dim3(256), 0, (hipStream_t)stream, B, idx, adv,
-                       out);
-    return hipGetLastError();
+int salp_ppo_mlp_adv_partials(int64_t batch, int64_t n_minibatches, const int64_t* idx, const float* advantages,
+                              double* out, void* stream) {
+    // n_minibatches is the grid's y extent
+    if (batch <= 0 || n_minibatches <= 0 || n_minibatches > 65535)
+        return fail(SALP_EINVAL, "salp_ppo_mlp_adv_partials: batch > 0 and 0 < n_minibatches <= 65535");
+    if (!idx || !advantages || !out) return fail(SALP_EINVAL, "salp_ppo_mlp_adv_partials: null buffer");
+    hipLaunchKernelGGL(k_mlp_adv_sums, dim3(NADV, (unsigned)n_minibatches), dim3(256), 0, (hipStream_t)stream, batch,
+                       idx, advantages, out);
+    return check_hip(hipGetLastError(), "k_mlp_adv_sums");
 }
 
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_ppo_mlp_apply_launch(const SalpPpoAdam* o,
-                                                                                       void* stream) {
+int salp_ppo_mlp_apply(const SalpPpoAdam* o, void* stream) {
+    if (!o || !obs_dim_ok(o->obs_dim)) return fail(SALP_EINVAL, "salp_ppo_mlp_apply: obs_dim out of range");
+    if (!o->grads || !o->exp_avg || !o->exp_avg_sq || !o->step)
+        return fail(SALP_EINVAL, "salp_ppo_mlp_apply: null buffer");
+    for (int t = 0; t < SALP_MLP_N_TENSORS; ++t)
+        if (!o->params[t]) return fail(SALP_EINVAL, "salp_ppo_mlp_apply: null parameter tensor");
     const Layout L = make_layout(o->obs_dim);
     // 1 - beta in double, rounded once, as torch.optim.Adam passes it: formed in float32, 1.0f - (float)0.999 is
     // 1.29e-5 below 0.001 and exp_avg_sq was that far from torch's (tests/test_gpu_ppo_mlp_ref.py)
@@ -859,5 +886,7 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t salp_ppo_mlp_apply_l
     } else {
         hipLaunchKernelGGL(k_mlp_apply, dim3(1), dim3(NT_APPLY), 0, (hipStream_t)stream, *o, L, c1, c2);
     }
-    return hipGetLastError();
+    return check_hip(hipGetLastError(), "k_mlp_apply");
 }
+
+}  // extern "C"

@@ -28,7 +28,11 @@
 #include <cstdint>
 
 #include "../../include/salp.h"
+#include "salp_host.h"
 #include "salp_philox.h"
+
+using salp::check_hip;
+using salp::fail;
 
 /* Stream tag (Philox counter word 3) of the replay sampler, "RPLY".  The
  * tags of salp_philox.h are small integers or-ed with bits of the env id's
@@ -239,59 +243,88 @@ inline unsigned blocks_for(int64_t n, int64_t cap) {
     return (unsigned)(b < cap ? b : cap);
 }
 
+bool replay_ok(const SalpReplay* rb) {
+    // row indices stay far inside int64: capacity x n_envs x obs_dim elements are allocated by the caller
+    return rb && rb->capacity > 0 && rb->n_envs > 0 && rb->obs_dim > 0 && rb->obs_dim <= SALP_OBS_DIM_MAX &&
+           rb->n_envs <= INT32_MAX && rb->obs && rb->next_obs && rb->actions && rb->rewards && rb->dones && rb->pos &&
+           rb->size;
+}
+
 }  // namespace
 
-// Each returns the launch status (salp_ppo.hip explains why not a later hipGetLastError()).
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_replay_add_launch(const SalpReplay* rb,
-                                                                                    const SalpReplayAdd* a,
-                                                                                    void* stream) {
+extern "C" {
+
+// The launch status of each: one hipGetLastError() right after the launches (salp_ppo.hip explains why).
+int salp_replay_add(const SalpReplay* rb, const SalpReplayAdd* a, void* stream) {
+    if (!replay_ok(rb)) return fail(SALP_EINVAL, "salp_replay_add: bad replay buffer");
+    if (!a || !a->obs || !a->actions || !a->obs_after || !a->terminal_obs || !a->reward || !a->terminated ||
+        !a->truncated)
+        return fail(SALP_EINVAL, "salp_replay_add: null buffer");
     hipLaunchKernelGGL(k_replay_add, dim3(blocks_for(rb->n_envs, INT32_MAX)), dim3(kBlock), 0, (hipStream_t)stream,
                        *rb, *a);
-    return hipGetLastError();
+    return check_hip(hipGetLastError(), "k_replay_add");
 }
 
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_replay_sample_launch(const SalpReplay* rb,
-                                                                                       const SalpReplaySample* s,
-                                                                                       void* stream) {
+int salp_replay_sample(const SalpReplay* rb, const SalpReplaySample* s, void* stream) {
+    if (!replay_ok(rb)) return fail(SALP_EINVAL, "salp_replay_sample: bad replay buffer");
+    if (!s || s->batch <= 0 || s->batch > (int64_t)1 << 32)   // the row index is a 32-bit Philox counter word
+        return fail(SALP_EINVAL, "salp_replay_sample: batch must be in 1 .. 2^32");
+    if (!s->update || !s->obs || !s->next_obs || !s->actions || !s->rewards || !s->dones)
+        return fail(SALP_EINVAL, "salp_replay_sample: null buffer");
     hipLaunchKernelGGL(k_replay_sample, dim3(blocks_for(s->batch * 32, INT32_MAX)), dim3(kBlock), 0,
                        (hipStream_t)stream, *rb, *s);
-    return hipGetLastError();
+    return check_hip(hipGetLastError(), "k_replay_sample");
 }
 
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_sac_actor_fwd_launch(
-    int64_t B, const float* mu, const float* log_std, const float* eps, float* act, float* logp, void* stream) {
-    hipLaunchKernelGGL(k_actor_fwd, dim3(blocks_for(B, INT32_MAX)), dim3(kBlock), 0, (hipStream_t)stream, B, mu,
-                       log_std, eps, act, logp);
-    return hipGetLastError();
+int salp_sac_actor_head_forward(int64_t batch, const float* mu, const float* log_std, const float* eps,
+                                float* act, float* logp, void* stream) {
+    if (batch <= 0) return fail(SALP_EINVAL, "salp_sac_actor_head_forward: batch must be positive");
+    if (!mu || !log_std || !eps || !act || !logp)
+        return fail(SALP_EINVAL, "salp_sac_actor_head_forward: null buffer");
+    hipLaunchKernelGGL(k_actor_fwd, dim3(blocks_for(batch, INT32_MAX)), dim3(kBlock), 0, (hipStream_t)stream, batch,
+                       mu, log_std, eps, act, logp);
+    return check_hip(hipGetLastError(), "k_actor_fwd");
 }
 
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_sac_actor_bwd_launch(
-    int64_t B, const float* log_std, const float* eps, const float* act, const float* da, const float* dlogp,
-    float* dmu, float* dls, void* stream) {
-    hipLaunchKernelGGL(k_actor_bwd, dim3(blocks_for(B, INT32_MAX)), dim3(kBlock), 0, (hipStream_t)stream, B, log_std,
-                       eps, act, da, dlogp, dmu, dls);
-    return hipGetLastError();
+int salp_sac_actor_head_backward(int64_t batch, const float* log_std, const float* eps, const float* act,
+                                 const float* da, const float* dlogp, float* dmu, float* dls, void* stream) {
+    if (batch <= 0) return fail(SALP_EINVAL, "salp_sac_actor_head_backward: batch must be positive");
+    if (!log_std || !eps || !act || !dmu || !dls)
+        return fail(SALP_EINVAL, "salp_sac_actor_head_backward: null buffer");
+    hipLaunchKernelGGL(k_actor_bwd, dim3(blocks_for(batch, INT32_MAX)), dim3(kBlock), 0, (hipStream_t)stream, batch,
+                       log_std, eps, act, da, dlogp, dmu, dls);
+    return check_hip(hipGetLastError(), "k_actor_bwd");
 }
 
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_sac_td_launch(const SalpSacTd* t, void* stream) {
+int salp_sac_td_head(const SalpSacTd* t, void* stream) {
+    if (!t || t->batch <= 0) return fail(SALP_EINVAL, "salp_sac_td_head: batch must be positive");
+    if (!t->rewards || !t->dones || !t->q1_target || !t->q2_target || !t->logp_next || !t->q1 || !t->q2 || !t->logp ||
+        !t->log_alpha || !t->workspace || !t->target || !t->dq1 || !t->dq2 || !t->out || !t->alpha_used)
+        return fail(SALP_EINVAL, "salp_sac_td_head: null buffer");
     const unsigned g = blocks_for(t->batch, kGrid);
     hipLaunchKernelGGL(k_td_rows, dim3(g), dim3(kBlock), 0, (hipStream_t)stream, *t, (float)t->gamma);
     hipLaunchKernelGGL(k_td_final, dim3(1), dim3(kBlock), 0, (hipStream_t)stream, *t, (int)g);
-    return hipGetLastError();
+    return check_hip(hipGetLastError(), "k_td");
 }
 
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_sac_pi_launch(const SalpSacPi* p, void* stream) {
+int salp_sac_pi_head(const SalpSacPi* p, void* stream) {
+    if (!p || p->batch <= 0) return fail(SALP_EINVAL, "salp_sac_pi_head: batch must be positive");
+    if (!p->alpha_used || !p->logp || !p->q1_pi || !p->q2_pi || !p->workspace || !p->out || !p->dlogp || !p->dq1 ||
+        !p->dq2)
+        return fail(SALP_EINVAL, "salp_sac_pi_head: null buffer");
     const unsigned g = blocks_for(p->batch, kGrid);
     hipLaunchKernelGGL(k_pi_rows, dim3(g), dim3(kBlock), 0, (hipStream_t)stream, *p);
     hipLaunchKernelGGL(k_pi_final, dim3(1), dim3(kBlock), 0, (hipStream_t)stream, *p, (int)g);
-    return hipGetLastError();
+    return check_hip(hipGetLastError(), "k_pi");
 }
 
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_sac_polyak_launch(int64_t n, const float* params,
-                                                                                    float* target, double tau,
-                                                                                    void* stream) {
+int salp_sac_polyak(int64_t n, const float* params, float* target, double tau, void* stream) {
+    if (n <= 0 || !params || !target) return fail(SALP_EINVAL, "salp_sac_polyak: bad argument");
+    if (!(tau >= 0 && tau <= 1)) return fail(SALP_EINVAL, "salp_sac_polyak: tau must be in [0, 1]");
     // 1 - tau in double, then rounded: 1.0f - (float)0.005 is 1.1e-8 away from it
     hipLaunchKernelGGL(k_polyak, dim3(blocks_for(n, 1024)), dim3(kBlock), 0, (hipStream_t)stream, n, params, target,
                        (float)tau, (float)(1.0 - tau));
-    return hipGetLastError();
+    return check_hip(hipGetLastError(), "k_polyak");
 }
+
+}  // extern "C"

@@ -34,6 +34,10 @@
 #include <cstdint>
 
 #include "../../include/salp.h"
+#include "salp_host.h"
+
+using salp::check_hip;
+using salp::fail;
 
 namespace {
 
@@ -413,32 +417,81 @@ inline int blocks_of(int64_t B) {
     return (int)(t < MAXB ? t : MAXB);
 }
 
+bool sac_net_dims_ok(int in, int od) {
+    return in >= 1 && in <= SALP_SAC_NET_IN_MAX && od >= 1 && od <= SALP_SAC_NET_OUT_MAX;
+}
+// the part SalpSacNetForward and SalpSacNetBackward share; nullptr if it is sound, else what is wrong
+const char* sac_net_bad(int64_t batch, int d0, int d1, int od, int n_nets, const float* const* params,
+                        const float* const* x0, const float* const* x1) {
+    if (batch <= 0 || batch > INT32_MAX) return "batch must be in 1 .. 2^31 - 1";
+    if (d0 < 1 || d1 < 0 || !sac_net_dims_ok(d0 + d1, od)) return "d0 >= 1, d1 >= 0, d0 + d1 <= 17 and out_dim in 1 .. 6";
+    if (n_nets < 1 || n_nets > SALP_SAC_NET_MAX_NETS) return "n_nets must be in 1 .. 4";
+    for (int i = 0; i < n_nets; ++i)
+        if (!params[i] || !x0[i] || (d1 > 0 && !x1[i])) return "null params, x0 or x1";
+    return nullptr;
+}
+
 }  // namespace
 
-extern "C" __attribute__((visibility("hidden"))) int salp_sac_net_tile_rows_impl(void) { return TR; }
-extern "C" __attribute__((visibility("hidden"))) int salp_sac_net_max_blocks_impl(void) { return MAXB; }
-extern "C" __attribute__((visibility("hidden"))) int64_t salp_sac_net_offset_impl(int in, int od, int tensor) {
-    const int64_t size[SALP_SAC_NET_N_TENSORS] = {(int64_t)H * in, H, (int64_t)H * H, H, (int64_t)od * H, od};
+extern "C" {
+
+int64_t salp_sac_net_num_params(int in_dim, int out_dim) {
+    return salp_sac_net_offset(in_dim, out_dim, SALP_SAC_NET_N_TENSORS);
+}
+
+int64_t salp_sac_net_offset(int in_dim, int out_dim, int tensor) {
+    if (!sac_net_dims_ok(in_dim, out_dim) || tensor < 0 || tensor > SALP_SAC_NET_N_TENSORS) {
+        fail(SALP_EINVAL, "salp_sac_net_offset: in_dim in 1 .. 17, out_dim in 1 .. 6, tensor in 0 .. 6");
+        return -1;
+    }
+    const int64_t size[SALP_SAC_NET_N_TENSORS] = {(int64_t)H * in_dim, H, (int64_t)H * H, H, (int64_t)out_dim * H,
+                                                  out_dim};
     int64_t off = 0;
     for (int t = 0; t < tensor; ++t) off += size[t];
     return off;
 }
-// [n_nets][blocks][P] parameter partials, then [n_nets][batch][d1] dx1 partials
-extern "C" __attribute__((visibility("hidden"))) int64_t salp_sac_net_workspace_impl(int64_t B, int d0, int d1, int od,
-                                                                                     int n_nets) {
-    return (int64_t)n_nets * blocks_of(B) * num_params(d0 + d1, od) + (int64_t)n_nets * B * d1;
+
+int salp_sac_net_tile_rows(void) { return TR; }
+int salp_sac_net_max_blocks(void) { return MAXB; }
+
+int64_t salp_sac_net_workspace_floats(int64_t batch, int d0, int d1, int out_dim, int n_nets) {
+    if (batch <= 0 || batch > INT32_MAX || d0 < 1 || d1 < 0 || !sac_net_dims_ok(d0 + d1, out_dim) || n_nets < 1 ||
+        n_nets > SALP_SAC_NET_MAX_NETS) {
+        fail(SALP_EINVAL, "salp_sac_net_workspace_floats: bad argument");
+        return -1;
+    }
+    // [n_nets][blocks][P] parameter partials, then [n_nets][batch][d1] dx1 partials
+    return (int64_t)n_nets * blocks_of(batch) * num_params(d0 + d1, out_dim) + (int64_t)n_nets * batch * d1;
 }
 
-// Each returns the launch status (salp_ppo.hip explains why not a later hipGetLastError()).
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_sac_net_fwd_launch(const SalpSacNetForward* f,
-                                                                                     void* stream) {
+// The launch status of each: one hipGetLastError() right after the launches (salp_ppo.hip explains why).
+int salp_sac_net_forward(const SalpSacNetForward* f, void* stream) {
+    if (!f) return fail(SALP_EINVAL, "salp_sac_net_forward: null argument");
+    if (const char* bad = sac_net_bad(f->batch, f->d0, f->d1, f->out_dim, f->n_nets, f->params, f->x0, f->x1))
+        return fail(SALP_EINVAL, std::string("salp_sac_net_forward: ") + bad);
+    for (int i = 0; i < f->n_nets; ++i) {
+        if (!f->out[i]) return fail(SALP_EINVAL, "salp_sac_net_forward: null out");
+        if (!f->h1[i] != !f->h2[i])
+            return fail(SALP_EINVAL, "salp_sac_net_forward: h1 and h2 are both NULL or both set");
+    }
     hipLaunchKernelGGL(k_sac_net_fwd, dim3((unsigned)tiles_of(f->batch), (unsigned)f->n_nets), dim3(NT), 0,
                        (hipStream_t)stream, *f);
-    return hipGetLastError();
+    return check_hip(hipGetLastError(), "k_sac_net_fwd");
 }
 
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_sac_net_bwd_launch(const SalpSacNetBackward* b,
-                                                                                     void* stream) {
+int salp_sac_net_backward(const SalpSacNetBackward* b, void* stream) {
+    if (!b) return fail(SALP_EINVAL, "salp_sac_net_backward: null argument");
+    if (const char* bad = sac_net_bad(b->batch, b->d0, b->d1, b->out_dim, b->n_nets, b->params, b->x0, b->x1))
+        return fail(SALP_EINVAL, std::string("salp_sac_net_backward: ") + bad);
+    for (int i = 0; i < b->n_nets; ++i) {
+        if (!b->h1[i] || !b->h2[i] || !b->dout[i])
+            return fail(SALP_EINVAL, "salp_sac_net_backward: null h1, h2 or dout");
+        if (!b->dparams[i] != !b->dparams[0])
+            return fail(SALP_EINVAL, "salp_sac_net_backward: dparams are all NULL or all set");
+    }
+    if (!b->dparams[0] && !b->dx1) return fail(SALP_EINVAL, "salp_sac_net_backward: neither dparams nor dx1 is set");
+    if (b->dx1 && b->d1 == 0) return fail(SALP_EINVAL, "salp_sac_net_backward: dx1 needs d1 > 0");
+    if (!b->workspace) return fail(SALP_EINVAL, "salp_sac_net_backward: null workspace");
     hipStream_t s = (hipStream_t)stream;
     const int nb = blocks_of(b->batch);
     const int64_t P = num_params(b->d0 + b->d1, b->out_dim), tiles = tiles_of(b->batch);
@@ -448,10 +501,12 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t salp_sac_net_bwd_lau
     const dim3 grid((unsigned)nb, (unsigned)b->n_nets);
     if (wg) hipLaunchKernelGGL(k_sac_net_bwd<true>, grid, dim3(NTB), 0, s, *b, tiles, P, part, dxp);
     else hipLaunchKernelGGL(k_sac_net_bwd<false>, grid, dim3(NTB), 0, s, *b, tiles, P, part, dxp);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
+    // the reduction is not enqueued behind a backward that did not launch
+    if (const int rc = check_hip(hipGetLastError(), "k_sac_net_bwd")) return rc;
     const int64_t nx = b->dx1 ? b->batch * b->d1 : 0, n = wg && P > nx ? P : nx;
     hipLaunchKernelGGL(k_sac_net_reduce, dim3((unsigned)((n + NT_RED - 1) / NT_RED), (unsigned)b->n_nets + 1),
                        dim3(NT_RED), 0, s, *b, nb, P, part, dxp);
-    return hipGetLastError();
+    return check_hip(hipGetLastError(), "k_sac_net_bwd");
 }
+
+}  // extern "C"

@@ -15,18 +15,18 @@
 
 #include <stdint.h>
 
-// Temporary storage bytes for sorting n (uint32 key, int32 id) pairs.
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_sort_temp_bytes(int64_t n, size_t* bytes) {
+#include "salp_sort.h"
+
+// Both are hidden: salp_sort.h declares them so.
+extern "C" hipError_t salp_sort_temp_bytes(int64_t n, size_t* bytes) {
     *bytes = 0;
     return hipcub::DeviceRadixSort::SortPairsDescending(nullptr, *bytes, (const uint32_t*)nullptr,
                                                         (uint32_t*)nullptr, (const int32_t*)nullptr,
                                                         (int32_t*)nullptr, (int)n, 0, 16, (hipStream_t)nullptr);
 }
 
-// keys (predicted ticks, < 2^16) descending, carrying the env ids into `order`.
-extern "C" __attribute__((visibility("hidden"))) hipError_t salp_sort_launch(
-    void* temp, size_t temp_bytes, const uint32_t* keys_in, uint32_t* keys_out, const int32_t* ids_in,
-    int32_t* order, int64_t n, void* stream) {
+extern "C" hipError_t salp_sort_launch(void* temp, size_t temp_bytes, const uint32_t* keys_in, uint32_t* keys_out,
+                                       const int32_t* ids_in, int32_t* order, int64_t n, void* stream) {
     size_t bytes = temp_bytes;
     return hipcub::DeviceRadixSort::SortPairsDescending(temp, bytes, keys_in, keys_out, ids_in, order, (int)n, 0, 16,
                                                         (hipStream_t)stream);

@@ -193,7 +193,7 @@ class _Guarded:
 
 # ------------------------------------------------------------------ 1. spikes
 def _geometry(B):
-    """salp_ppo_mlp_grads_launch's split: (blocks, rows per block, blocks that carry rows)."""
+    """salp_ppo_mlp_grads' split (csrc/salp_ppo_mlp.hip): (blocks, rows per block, blocks that carry rows)."""
     tiles = -(-B // TR)
     nb = min(tiles, NB_MAX)
     rpb = -(-tiles // nb) * TR

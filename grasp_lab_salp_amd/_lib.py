@@ -235,6 +235,37 @@ class SalpSacNetBackward(ctypes.Structure):
     ]
 
 
+LSTM_POLICY_HIDDEN = 256     # include/salp.h SALP_LSTM_POLICY_HIDDEN
+LSTM_POLICY_MLP = 64         # include/salp.h SALP_LSTM_POLICY_MLP
+LSTM_POLICY_OBS_MAX = 16     # include/salp.h SALP_LSTM_POLICY_OBS_MAX
+LSTM_POLICY_ACT_DIM = 3      # include/salp.h SALP_LSTM_POLICY_ACT_DIM
+
+
+class SalpLstmPolicyNet(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p) for name in (
+        "weight_ih", "weight_hh", "bias_ih", "bias_hh", "mlp_w1", "mlp_b1", "mlp_w2", "mlp_b2", "head_w", "head_b")]
+
+
+class SalpLstmPolicyStep(ctypes.Structure):
+    _fields_ = [
+        ("rows", ctypes.c_int64),
+        ("obs_dim", ctypes.c_int32),
+        ("act_dim", ctypes.c_int32),
+        ("obs", ctypes.c_void_p),
+        ("keep", ctypes.c_void_p),
+        ("state_in", ctypes.c_void_p),
+        ("state_out", ctypes.c_void_p),
+        ("latent", ctypes.c_void_p),
+        ("actor", SalpLstmPolicyNet),
+        ("critic", SalpLstmPolicyNet),
+        ("log_std", ctypes.c_void_p),
+        ("eps", ctypes.c_void_p),
+        ("action", ctypes.c_void_p),
+        ("log_prob", ctypes.c_void_p),
+        ("value", ctypes.c_void_p),
+    ]
+
+
 EPWIN_COLS = 20           # include/salp.h SALP_EPWIN_COLS
 EPWIN_MAX_WINDOW = 1024   # include/salp.h SALP_EPWIN_MAX_WINDOW
 EPSUM_DIM = 84            # include/salp.h SALP_EPSUM_DIM
@@ -301,7 +332,8 @@ SIGNATURES = {
     "salp_lstm_cell_backward": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
     "salp_lstm_step_forward": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
     "salp_lstm_step_backward": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32] + [_V] * 11),
-    "salp_set_lockstep_order": (ctypes.c_int, [_H, ctypes.c_int]),
+    "salp_lstm_policy_step": (ctypes.c_int, [ctypes.POINTER(SalpLstmPolicyStep), _V]),
+    "salp_set_lockstep_order":(ctypes.c_int, [_H, ctypes.c_int]),
     "salp_set_rollout_kernel": (ctypes.c_int, [_H, ctypes.c_int]),
     "salp_set_step_kernel": (ctypes.c_int, [_H, ctypes.c_int]),
     "salp_pair_timeouts": (ctypes.c_int, [_H, ctypes.POINTER(ctypes.c_uint64), _V]),

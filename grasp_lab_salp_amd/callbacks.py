@@ -1,6 +1,8 @@
-"""Training callbacks for :class:`~grasp_lab_salp_amd.sac.SAC` with SB3's names
-and constructor arguments, so the reference's production script
-(src/train_robot.py:71-122) changes only its import line::
+"""Training callbacks for :class:`~grasp_lab_salp_amd.sac.SAC` and
+:class:`~grasp_lab_salp_amd.recurrent_ppo.RecurrentPPO` with SB3's names
+and constructor arguments, so the reference's training scripts
+(src/train_robot.py:71-122, src/train_robot_recurrent_ppo.py:110-165) change
+only their import lines::
 
     from grasp_lab_salp_amd.callbacks import (CheckpointCallback, EvalCallback, CallbackList,
                                               DetailedMetricsCallback)

@@ -61,6 +61,19 @@ def compute_gae(rewards, values, episode_starts, last_values, dones, gamma=0.99,
     """SB3 ``compute_returns_and_advantage`` on the GPU (``salp_gae``).
     All inputs float32 CUDA tensors, [n_steps, n_envs] / [n_envs]."""
     T, n = rewards.shape
+    if not rewards.is_cuda:
+        # CPU tensors (the host tests' stub env): SB3's loop in torch ops
+        adv = torch.empty_like(rewards) if advantages is None else advantages
+        ret = torch.empty_like(rewards) if returns is None else returns
+        last = torch.zeros_like(last_values)
+        for t in reversed(range(T)):
+            nonterminal = 1.0 - (dones if t == T - 1 else episode_starts[t + 1])
+            nxt = last_values if t == T - 1 else values[t + 1]
+            delta = rewards[t] + gamma * nxt * nonterminal - values[t]
+            last = delta + gamma * gae_lambda * nonterminal * last
+            adv[t] = last
+        torch.add(adv, values, out=ret)
+        return adv, ret
     for name, t, shape in (("rewards", rewards, (T, n)), ("values", values, (T, n)),
                            ("episode_starts", episode_starts, (T, n)), ("last_values", last_values, (n,)),
                            ("dones", dones, (n,))):
@@ -452,6 +465,11 @@ class PPO:
         self.logger = {}
         self.timing = {"collect_s": 0.0, "gae_s": 0.0, "train_s": 0.0}
         self.history = []   # per iteration: losses, finished-episode mean return, diverged envs
+        # callbacks (RecurrentPPO.learn; the lock-step collection calls _on_env_step after every env-step)
+        self._on_env_step = None
+        self.locals = {}               # the last env-step's device tensors, for callbacks
+        self.callback_metrics = {}     # the latest value of every key a callback recorded
+        self._recorded = {}            # ... those since the last history row
 
     # --------------------------------------------- fused minibatch step
     def _init_fused(self, lr):
@@ -537,18 +555,23 @@ class PPO:
         HIP events (start, before GAE, after GAE) on the current stream, so
         the split of the GPU timeline is attributed to the right phase."""
         b, sim = self.buf, self.sim
-        stream = torch.cuda.current_stream(self.device)
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-        ev[0].record(stream)
+        gpu = self.device.type == "cuda"   # (a CPU learner, the host tests' stub env: no events)
+        stream = torch.cuda.current_stream(self.device) if gpu else None
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if gpu else []
+        if gpu:
+            ev[0].record(stream)
         if self._obs is None:
             self._obs = sim.reset()
         self._ep_stats.zero_()
         if self.collect == "chained":
             return self._collect_chained(ev, stream)
+        hook = self._on_env_step
         for t in range(self.n_steps):
             obs = self._obs
             a, v, lp = self._act(t, obs)
             r = sim.step(torch.clamp(a, self.low, self.high), auto_reset=True, want_terminal_obs=True)
+            if hook is not None:   # the flags as the task set them: the divergence guard marks its envs below
+                flags = r.terminated.to(torch.uint8), r.truncated.to(torch.uint8)
             rew = r.reward.float()
             reached = r.terminated.clone()   # the task's own termination: target reached
             bad = None
@@ -573,12 +596,21 @@ class PPO:
             b.log_probs[t].copy_(lp)
             self._obs = r.obs
             self._episode_starts = done.float()
+            if hook is not None:
+                self.num_timesteps += self.n_envs
+                self.locals = {"obs": r.obs, "actions": a, "rewards": r.reward, "terminated": flags[0],
+                               "truncated": flags[1], "dones": (flags[0] | flags[1]).bool(), "info": r.info,
+                               "diverged": (torch.zeros_like(flags[0]) if bad is None else bad.to(torch.uint8))}
+                if not hook():
+                    return None   # training ends after this env-step: no GAE, no update
         with torch.no_grad():
             last_values = self._last_values().contiguous()
-        ev[1].record(stream)
+        if gpu:
+            ev[1].record(stream)
         compute_gae(b.rewards, b.values, b.episode_starts, last_values, self._episode_starts.contiguous(),
                     self.gamma, self.gae_lambda, b.advantages, b.returns)
-        ev[2].record(stream)
+        if gpu:
+            ev[2].record(stream)
         return ev
 
     # hooks of the lock-step collection (RecurrentPPO carries LSTM states through them)
@@ -858,10 +890,31 @@ class PPO:
         phase timings come from HIP events on the stream (collection, GAE and
         update are attributed where the GPU ran them); ``history`` gets one
         row per iteration."""
+        return self._learn(total_timesteps, log_interval)
+
+    def record(self, key, value):
+        """A callback's ``logger.record``: kept in ``callback_metrics`` (latest
+        values) and added to the next ``history`` row."""
+        self.callback_metrics[key] = value
+        self._recorded[key] = value
+
+    def _learn(self, total_timesteps, log_interval=1, on_env_step=None):
+        """learn(); ``on_env_step`` (lock-step collection only) is called after
+        every env-step on the collection stream with ``locals`` set and
+        ``num_timesteps`` advanced by n_envs; False ends training after that
+        env-step, before the update."""
+        self._on_env_step = on_env_step
+        try:
+            return self._learn_loop(total_timesteps, log_interval)
+        finally:
+            self._on_env_step = None
+
+    def _learn_loop(self, total_timesteps, log_interval):
         it = 0
         start_steps = self.num_timesteps
-        stream = torch.cuda.current_stream(self.device)
-        if self._collect_stream is None and self.device.type == "cuda":
+        gpu = self.device.type == "cuda"
+        stream = torch.cuda.current_stream(self.device) if gpu else None
+        if self._collect_stream is None and gpu:
             self._collect_stream = torch.cuda.Stream(self.device)
             self._train_stream = torch.cuda.Stream(self.device)
         while self.num_timesteps < total_timesteps:
@@ -878,6 +931,8 @@ class PPO:
                 stream.wait_stream(cs)
             else:
                 ev = self.collect_rollouts()
+            if ev is None:   # a callback ended training inside the collection
+                break
             if self._train_stream is not None:
                 # the update (warm-up, captures and replays) on a stream the
                 # learner owns: eager work a caller issues between learn()
@@ -890,13 +945,15 @@ class PPO:
                 stream.wait_stream(ts)
             else:
                 self.logger = self.train()
-            end = torch.cuda.Event(enable_timing=True)
-            end.record(stream)
-            end.synchronize()
-            self.timing["collect_s"] += ev[0].elapsed_time(ev[1]) / 1e3
-            self.timing["gae_s"] += ev[1].elapsed_time(ev[2]) / 1e3
-            self.timing["train_s"] += ev[2].elapsed_time(end) / 1e3
-            self.num_timesteps += self.n_steps * self.n_envs
+            if gpu:
+                end = torch.cuda.Event(enable_timing=True)
+                end.record(stream)
+                end.synchronize()
+                self.timing["collect_s"] += ev[0].elapsed_time(ev[1]) / 1e3
+                self.timing["gae_s"] += ev[1].elapsed_time(ev[2]) / 1e3
+                self.timing["train_s"] += ev[2].elapsed_time(end) / 1e3
+            if self._on_env_step is None:   # (else the collection advanced it env-step by env-step)
+                self.num_timesteps += self.n_steps * self.n_envs
             it += 1
             if self.collect == "chained":
                 # the two-wave collection kernel never hangs the GPU: a wave that
@@ -909,6 +966,9 @@ class PPO:
                    "success_rate": n_succ / n_ep if n_ep else None,
                    "ep_len_mean": len_sum / n_ep if n_ep else None,
                    "diverged_envs": int(self._nonfinite - div0)}
+            if self._recorded:   # what callbacks recorded since the last row
+                row.update(self._recorded)
+                self._recorded = {}
             self.history.append(row)
             if self.verbose and it % log_interval == 0:
                 print(row, flush=True)

@@ -409,6 +409,69 @@ int salp_lstm_step_backward(int64_t rows, int32_t hidden, const float* act, cons
                             const float* c, const float* d_out, const float* dhk_next, const float* keep_next,
                             const float* dc, float* dgates, float* dc_prev, void* stream);
 
+/* One step of the whole recurrent policy (RecurrentActorCritic.act /
+ * predict_values, grasp_lab_salp_amd/recurrent_ppo.py) for `rows` envs:
+ * observation and LSTM state in; action, log-prob, value and new state out.
+ * Per network (actor, critic; either may be absent: all its pointers NULL):
+ *   hk = h keep, ck = c keep
+ *   gates = x W_ih^T + b_ih + b_hh + hk W_hh^T          (i, f, g, o)
+ *   c' = sigmoid(f) ck + sigmoid(i) tanh(g), h' = sigmoid(o) tanh(c')   (the cell above)
+ *   y = head(tanh(W2 tanh(W1 h' + b1) + b2))            (64-64 tanh MLP)
+ * actor: mean = y [3], a = mean + exp(log_std) eps (eps NULL: a = mean),
+ * log_prob = sum -(a - mean)^2 / (2 sigma^2) - log sigma - log sqrt(2 pi);
+ * critic: value = y [1].  The action is not clipped.
+ *
+ * Two launches on the caller's stream: k_lstm_policy_cell (the gate products
+ * of [hk | x | 1] on v_mfma_f32_32x32x2_f32, exact f32, K split over four
+ * accumulators; a workgroup owns 32 units of one network and keeps their
+ * weights in registers over its row tiles) and k_lstm_policy_head (MLP, head
+ * and Gaussian on the VALU).  float32, no atomics (two calls give identical
+ * bits), nothing allocated or synchronised.  The parameter pointers are the
+ * torch tensors as they are (weight_hh_l0, mlp weights 16-byte aligned).
+ * Rows >= rows and outputs whose pointer is NULL are never written.
+ * SALP_EINVAL before any launch for: bad sizes, a needed pointer that is NULL,
+ * a network given in part, both networks absent, an output of an absent
+ * network, nothing to compute, state_out == NULL without latent, and
+ * state_out overlapping state_in (a row's units are spread over workgroups:
+ * an in-place update would race; the caller double-buffers).  rows == 0 is
+ * SALP_OK.  Added under ABI 14 without a new version number: a library built
+ * before it is recognised by the missing symbol. */
+#define SALP_LSTM_POLICY_HIDDEN 256
+#define SALP_LSTM_POLICY_MLP 64
+#define SALP_LSTM_POLICY_OBS_MAX 16
+#define SALP_LSTM_POLICY_ACT_DIM 3
+typedef struct SalpLstmPolicyNet {
+    const float* weight_ih;   /* [1024][obs_dim]  torch weight_ih_l0 */
+    const float* weight_hh;   /* [1024][256]      torch weight_hh_l0 */
+    const float* bias_ih;     /* [1024] */
+    const float* bias_hh;     /* [1024] */
+    const float* mlp_w1;      /* [64][256] */
+    const float* mlp_b1;      /* [64] */
+    const float* mlp_w2;      /* [64][64] */
+    const float* mlp_b2;      /* [64] */
+    const float* head_w;      /* actor [3][64], critic [1][64] */
+    const float* head_b;      /* actor [3], critic [1] */
+} SalpLstmPolicyNet;
+typedef struct SalpLstmPolicyStep {
+    int64_t rows;
+    int32_t obs_dim;          /* 1 .. SALP_LSTM_POLICY_OBS_MAX */
+    int32_t act_dim;          /* SALP_LSTM_POLICY_ACT_DIM */
+    const float* obs;         /* [rows][obs_dim] */
+    const float* keep;        /* [rows] 1 - episode start; NULL: all 1 */
+    const float* state_in;    /* [4][rows][256]: actor h, actor c, critic h, critic c */
+    float* state_out;         /* the same shape; NULL: the state is not advanced */
+    float* latent;            /* [2][rows][256] h' of (actor, critic) between the launches;
+                                 needed only when state_out is NULL */
+    SalpLstmPolicyNet actor;
+    SalpLstmPolicyNet critic;
+    const float* log_std;     /* [3] */
+    const float* eps;         /* [rows][3] N(0, 1) noise; NULL: deterministic */
+    float* action;            /* [rows][3] or NULL */
+    float* log_prob;          /* [rows] or NULL */
+    float* value;             /* [rows] or NULL */
+} SalpLstmPolicyStep;
+int salp_lstm_policy_step(const SalpLstmPolicyStep* s, void* stream);
+
 /* ------------------------------------------------ SAC (ABI 14)
  * The off-policy learner of src/train_robot.py:62-69 (stable_baselines3 SAC,
  * "MlpPolicy", buffer_size 100 000, batch_size 256, tau 0.005, gamma 0.99;

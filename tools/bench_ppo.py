@@ -17,6 +17,19 @@ The reference's RecurrentPPO uses n_steps 2048, batch 64 with 4 envs
 starts, values, log-probs, advantages, returns = 19 floats per (step, env),
 5.1 GB) fits in HBM easily; batch 64 would mean 1 048 576 minibatches per
 epoch, so the batch is scaled with the env count (default 32 768).
+
+    python tools/bench_ppo.py --recurrent --reference-config [--fused-step]
+    python tools/bench_ppo.py --recurrent --ab-fused-step OUT.json [--reference-config | --n-envs ...]
+
+--reference-config: the reference script's own settings (4 envs, n_steps 2048,
+batch_size 64, seq_len 16).  --fused-step: RecurrentPPO(fused_step=True), the
+policy step as salp_lstm_policy_step.  --ab-fused-step: two learners of the
+same settings in this one process, fused_step off and on, one warm-up
+iteration each and then --iters timed iterations each in turn (off, on, off,
+on, ...); env-steps/s and the collect / GAE / update seconds of every
+iteration (HIP events) are printed as one JSON line and written to OUT.json.
+--collect-only K: K lock-step env-steps of one collection and nothing else
+(for a kernel trace: the launches per env-step are the difference of two K).
 """
 import argparse
 import json
@@ -57,6 +70,51 @@ def gae_roofline(T, n, reps=20):
                          "frac": gbs / HBM_PEAK_GBS}}
 
 
+def recurrent_ab(a):
+    """--ab-fused-step / --collect-only (see the module docstring); one GPU."""
+    from grasp_lab_salp_amd.recurrent_ppo import RecurrentPPO
+    from grasp_lab_salp_amd.vec_env import SalpVecEnv
+
+    def make(fused):
+        env = SalpVecEnv(a.n_envs, seed=0, infos=False)
+        return RecurrentPPO("MlpLstmPolicy", env, n_steps=a.n_steps, batch_size=a.batch_size, n_epochs=a.n_epochs,
+                            seed=0, seq_len=a.seq_len, policy_kwargs={"lstm_hidden_size": a.lstm_hidden},
+                            fused_step=fused)
+    if a.collect_only:
+        a.n_steps = a.collect_only - a.collect_only % a.seq_len
+        a.batch_size = a.seq_len
+        m = make(a.fused_step)
+        m.collect_rollouts()
+        torch.cuda.synchronize()
+        print(json.dumps({"collect_only_steps": a.n_steps, "n_envs": a.n_envs, "fused_step": a.fused_step}), flush=True)
+        return
+    per_iter = a.n_steps * a.n_envs
+    models = {"off": make(False), "on": make(True)}
+    rows = []
+    for r in range(a.iters + 1):       # round 0: warm-up (graph capture, allocator)
+        for name, m in models.items():
+            before = dict(m.timing)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            m.learn(m.num_timesteps + per_iter)
+            torch.cuda.synchronize()
+            el = time.perf_counter() - t0
+            row = {"fused_step": name, "round": r, "warmup": r == 0, "wall_s": el, "env_steps_per_s": per_iter / el,
+                   **{k: m.timing[k] - before[k] for k in m.timing}}
+            rows.append(row)
+            print(json.dumps(row), file=sys.stderr, flush=True)
+    res = {"metric": "RecurrentPPO iteration, fused_step off / on in turn (one process)", "n_envs": a.n_envs,
+           "n_steps": a.n_steps, "batch_size": a.batch_size, "n_epochs": a.n_epochs, "seq_len": a.seq_len,
+           "lstm_hidden": a.lstm_hidden, "iterations": rows}
+    for name in models:
+        timed = [x for x in rows if x["fused_step"] == name and not x["warmup"]]
+        res[name] = {k: sum(x[k] for x in timed) / len(timed) for k in ("env_steps_per_s", "collect_s", "gae_s",
+                                                                         "train_s", "wall_s")}
+    with open(a.ab_fused_step, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps({k: res[k] for k in ("metric", "n_envs", "n_steps", "off", "on")}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n-envs", type=int, default=32768)
@@ -74,7 +132,16 @@ def main():
                     help="RecurrentPPO with the MlpLstmPolicy (LSTM 256) of src/train_robot_recurrent_ppo.py")
     ap.add_argument("--lstm-hidden", type=int, default=256)
     ap.add_argument("--seq-len", type=int, default=16)
+    ap.add_argument("--fused-step", action="store_true", help="RecurrentPPO(fused_step=True)")
+    ap.add_argument("--reference-config", action="store_true",
+                    help="src/train_robot_recurrent_ppo.py:85-107: 4 envs, n_steps 2048, batch_size 64, seq_len 16")
+    ap.add_argument("--ab-fused-step", metavar="OUT.json", help="fused_step off / on in turn in one process")
+    ap.add_argument("--collect-only", type=int, default=0, metavar="K", help="one collection of K env-steps, no update")
     a = ap.parse_args()
+    if a.reference_config:
+        a.n_envs, a.n_steps, a.batch_size, a.seq_len, a.recurrent = 4, 2048, 64, 16, True
+    if a.ab_fused_step or a.collect_only:
+        return recurrent_ab(a)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -89,7 +156,8 @@ def main():
     if a.recurrent:
         from grasp_lab_salp_amd.recurrent_ppo import RecurrentPPO
         model = RecurrentPPO("MlpLstmPolicy", env, n_steps=a.n_steps, batch_size=a.batch_size, n_epochs=a.n_epochs,
-                             seed=0, seq_len=a.seq_len, policy_kwargs={"lstm_hidden_size": a.lstm_hidden})
+                             seed=0, seq_len=a.seq_len, policy_kwargs={"lstm_hidden_size": a.lstm_hidden},
+                             fused_step=a.fused_step)
     else:
         model = PPO("MlpPolicy", env, n_steps=a.n_steps, batch_size=a.batch_size, n_epochs=a.n_epochs, seed=0,
                     collect=a.collect, use_graphs=False if a.no_graphs else None)

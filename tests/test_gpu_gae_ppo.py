@@ -19,7 +19,10 @@ def _case(rng, T, n, p_start=0.05):
     return rew, val, st, lv, dn
 
 
-@pytest.mark.parametrize("T,n", [(1, 1), (1, 300), (5, 257), (16, 64), (37, 1000), (64, 4096)])
+# salp_gae picks 64-, 128- or 256-lane blocks by n: 65 280 is the last size on 128 lanes, 65 281 the first on
+# 256; T = 17 and 33 cross its ragged-top and whole-block paths
+@pytest.mark.parametrize("T,n", [(1, 1), (1, 300), (5, 257), (16, 64), (37, 1000), (64, 4096), (16, 65280),
+                                 (17, 65281), (33, 65537)])
 def test_gae_bit_identical_to_oracle(T, n):
     from grasp_lab_salp_amd.ppo import compute_gae
     rng = np.random.default_rng(T * 1000 + n)

@@ -96,7 +96,8 @@ def test_actor_head_equals_the_closed_form(B):
 
 
 # ------------------------------------------------------------- TD / pi heads
-@pytest.mark.parametrize("B", [1, 257, 4097])
+# (the heads cap their grid at 64 blocks of 256 rows: 16385 and 49153 are the second and fourth stride passes)
+@pytest.mark.parametrize("B", [1, 257, 4097, 16385, 49153])
 def test_td_and_pi_heads_equal_fp64(B):
     """Mixed dones, q1 == q2 ties in the target critics and in the actor pass.
     Float32 roundings per element, u = 2^-24, against float64 on the same
@@ -152,7 +153,8 @@ def test_td_and_pi_heads_equal_fp64(B):
 
 
 # -------------------------------------------------------------------- polyak
-@pytest.mark.parametrize("n", [1, 255, 70003])
+# (the grid is capped at 1024 blocks of 256 elements: 262145 and 524295 are the second and third stride passes)
+@pytest.mark.parametrize("n", [1, 255, 70003, 262145, 524295])
 def test_polyak_equals_fp64(n):
     """Within 2 ulp (float32) of target (1 - tau) + tau param in float64, the
     ulp taken at max(|target|, |param|): 1 - tau rounded from double (0.5), the

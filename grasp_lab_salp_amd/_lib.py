@@ -105,6 +105,20 @@ class SalpPpoAdam(ctypes.Structure):
     ]
 
 
+class SalpPpoMlpAct(ctypes.Structure):
+    _fields_ = [
+        ("rows", ctypes.c_int64),
+        ("obs_dim", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("params", ctypes.c_void_p * N_MLP_TENSORS),
+        ("obs", ctypes.c_void_p),
+        ("eps", ctypes.c_void_p),
+        ("action", ctypes.c_void_p),
+        ("log_prob", ctypes.c_void_p),
+        ("value", ctypes.c_void_p),
+    ]
+
+
 SAC_WORKSPACE_DOUBLES = 256   # include/salp.h SALP_SAC_WORKSPACE_DOUBLES
 
 
@@ -362,6 +376,7 @@ SIGNATURES = {
     "salp_ppo_mlp_grads": (ctypes.c_int, [ctypes.POINTER(SalpPpoMinibatch), _V]),
     "salp_ppo_mlp_apply": (ctypes.c_int, [ctypes.POINTER(SalpPpoAdam), _V]),
     "salp_ppo_mlp_adv_partials": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64, _V, _V, _V, _V]),
+    "salp_ppo_mlp_act": (ctypes.c_int, [ctypes.POINTER(SalpPpoMlpAct), _V]),
     "salp_replay_add": (ctypes.c_int, [ctypes.POINTER(SalpReplay), ctypes.POINTER(SalpReplayAdd), _V]),
     "salp_replay_sample": (ctypes.c_int, [ctypes.POINTER(SalpReplay), ctypes.POINTER(SalpReplaySample), _V]),
     "salp_sac_actor_head_forward": (ctypes.c_int, [ctypes.c_int64, _V, _V, _V, _V, _V, _V]),

@@ -1,4 +1,5 @@
-"""Training callbacks for :class:`~grasp_lab_salp_amd.sac.SAC` and
+"""Training callbacks for :class:`~grasp_lab_salp_amd.sac.SAC`,
+:class:`~grasp_lab_salp_amd.ppo.PPO` and
 :class:`~grasp_lab_salp_amd.recurrent_ppo.RecurrentPPO` with SB3's names
 and constructor arguments, so the reference's training scripts
 (src/train_robot.py:71-122, src/train_robot_recurrent_ppo.py:110-165) change
@@ -21,6 +22,18 @@ steps later: a callback consumes them inside ``_on_step``.  ``_on_step`` runs
 on the learner's collection stream.  ``logger.record(key, value)`` keeps the
 value in ``model.callback_metrics`` and adds it to the learner's next
 ``history`` row; no TensorBoard event file is written.
+
+:class:`~grasp_lab_salp_amd.ppo.PPO` with ``collect="chained"`` steps its envs
+inside one kernel launch per collection: there is no env-step boundary on the
+host to call ``on_step`` at.  It calls ``on_steps(n_steps)`` once per
+collection instead: ``n_calls`` advances by ``n_steps``, ``locals`` is empty,
+and ``_on_steps(first, last)`` receives the 1-based numbers of the calls
+covered.  ``CheckpointCallback`` and ``EvalCallback`` then fire once if a
+multiple of their frequency lies in ``[first, last]``, under the current
+``num_timesteps``.  A callback that overrides ``_on_step`` but not
+``_on_steps`` needs the per-step tensors (``DetailedMetricsCallback`` does):
+such a learner refuses it with ValueError when training starts; it runs under
+``collect="lockstep"``.
 """
 import os
 
@@ -63,6 +76,12 @@ class BaseCallback:
         self.model = model
         self.logger = _Logger(model)
         self.num_timesteps = model.num_timesteps
+        if getattr(model, "collect", None) == "chained":
+            per_step = self.per_step_only()
+            if per_step:
+                raise ValueError(f"{', '.join(per_step)}: _on_step needs every env-step's tensors, and the chained "
+                                 "collection has no env-step boundary on the host (callbacks run once per "
+                                 'collection, on_steps): build the learner with collect="lockstep"')
         self._init_callback()
 
     def _init_callback(self):
@@ -84,6 +103,31 @@ class BaseCallback:
 
     def _on_step(self):
         return True
+
+    def on_steps(self, k):
+        """``k`` vec-env steps at once (a learner without a per-step boundary
+        on the host: PPO's chained collection)."""
+        first = self.n_calls + 1
+        self.n_calls += int(k)
+        self.num_timesteps = self.model.num_timesteps
+        self.locals = {}
+        return bool(self._on_steps(first, self.n_calls))
+
+    def _on_steps(self, first, last):
+        """Calls ``first .. last`` (1-based, inclusive) have passed; False stops training."""
+        return True
+
+    def per_step_only(self):
+        """Class names of the callbacks here that work per env-step only:
+        ``_on_step`` overridden, ``_on_steps`` not."""
+        cls = type(self)
+        only = cls._on_step is not BaseCallback._on_step and cls._on_steps is BaseCallback._on_steps
+        return [cls.__name__] if only else []
+
+    @staticmethod
+    def _due(freq, first, last):
+        """Does a multiple of ``freq`` lie in ``[first, last]``?"""
+        return last // freq > (first - 1) // freq
 
     def on_training_end(self):
         self._on_training_end()
@@ -118,6 +162,15 @@ class CallbackList(BaseCallback):
             go_on = cb.on_step() and go_on
         return go_on
 
+    def _on_steps(self, first, last):
+        go_on = True
+        for cb in self.callbacks:
+            go_on = cb.on_steps(last - first + 1) and go_on
+        return go_on
+
+    def per_step_only(self):
+        return [name for cb in self.callbacks for name in cb.per_step_only()]
+
     def _on_training_end(self):
         for cb in self.callbacks:
             cb.on_training_end()
@@ -144,13 +197,21 @@ class CheckpointCallback(BaseCallback):
 
     def _on_step(self):
         if self.n_calls % self.save_freq == 0:
-            path = self._checkpoint_path()
-            self.model.save(path)
-            if self.verbose:
-                print(f"Saving model checkpoint to {path}", flush=True)
-            if self.save_replay_buffer:
-                self.model.save_replay_buffer(self._checkpoint_path("replay_buffer_", "pt"))
+            self._save()
         return True
+
+    def _on_steps(self, first, last):
+        if self._due(self.save_freq, first, last):
+            self._save()
+        return True
+
+    def _save(self):
+        path = self._checkpoint_path()
+        self.model.save(path)
+        if self.verbose:
+            print(f"Saving model checkpoint to {path}", flush=True)
+        if self.save_replay_buffer:
+            self.model.save_replay_buffer(self._checkpoint_path("replay_buffer_", "pt"))
 
 
 class EvalCallback(BaseCallback):
@@ -191,8 +252,16 @@ class EvalCallback(BaseCallback):
             os.makedirs(os.path.dirname(self.log_path), exist_ok=True)
 
     def _on_step(self):
-        if self.n_calls % self.eval_freq:
-            return True
+        if self.n_calls % self.eval_freq == 0:
+            self._evaluate()
+        return True
+
+    def _on_steps(self, first, last):
+        if self._due(self.eval_freq, first, last):
+            self._evaluate()
+        return True
+
+    def _evaluate(self):
         returns, lengths = self.model.evaluate(self.eval_env, n_eval_episodes=self.n_eval_episodes,
                                                deterministic=self.deterministic, return_episode_rewards=True)
         successes = (getattr(self.model, "last_eval", None) or {}).get("successes")
@@ -215,7 +284,6 @@ class EvalCallback(BaseCallback):
             self.best_mean_reward = mean
             if self.best_model_save_path is not None:
                 self.model.save(os.path.join(self.best_model_save_path, "best_model"))
-        return True
 
 
 # (recorded key, summary key) in the order of src/tensorboard_callback.py:136-205

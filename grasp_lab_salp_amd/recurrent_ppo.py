@@ -42,7 +42,7 @@ from torch import nn
 
 from . import _lib
 from ._abi import INFO_DIM
-from .ppo import PPO, SplitKLinear, _ortho, allreduce_gradients, ppo_loss
+from .ppo import PPO, SplitKLinear, _NoEnv, _ortho, allreduce_gradients, ppo_loss
 
 __all__ = ["RecurrentActorCritic", "RecurrentPPO", "FusedPolicyStep", "lstm_cell"]
 
@@ -379,18 +379,6 @@ class FusedPolicyStep:
         return (self.action if actor else None, self.log_prob if actor else None, value if critic else None)
 
 
-class _NoEnv:
-    """What the constructor reads of an env, for a predict-only model."""
-
-    n_envs = 1
-
-    def __init__(self, obs_dim, device):
-        self.obs_dim = int(obs_dim)
-        self.device = torch.device(device)
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-
-
 class RecurrentPPO(PPO):
     """sb3-contrib ``RecurrentPPO`` on a :class:`~grasp_lab_salp_amd.vec_env.SalpVecEnv`
     (see the module docstring for the semantics).  ``batch_size`` counts
@@ -515,18 +503,6 @@ class RecurrentPPO(PPO):
         cb.on_training_end()
         return self
 
-    def _as_callback(self, callback):
-        """None, a callback or a list of callbacks -> None or one initialised callback."""
-        if callback is None:
-            return None
-        from .callbacks import BaseCallback, CallbackList
-        if isinstance(callback, (list, tuple)):
-            callback = CallbackList(list(callback))
-        if not isinstance(callback, BaseCallback):
-            raise TypeError("callback: a grasp_lab_salp_amd.callbacks.BaseCallback, a list of them, or None")
-        callback.init_callback(self)
-        return callback
-
     # ----------------------------------------------- predict and evaluate
     @torch.no_grad()
     def _eval_action(self, obs, state, starts, deterministic=True):
@@ -627,11 +603,6 @@ class RecurrentPPO(PPO):
     FORMAT, FORMAT_VERSION = "grasp_lab_salp_amd.RecurrentPPO", 1
     _HYPERPARAMETERS = ("learning_rate", "n_steps", "batch_size", "n_epochs", "gamma", "gae_lambda", "clip_range",
                         "ent_coef", "vf_coef", "max_grad_norm", "normalize_advantage", "reset_nonfinite", "seq_len")
-
-    @staticmethod
-    def _zip_path(path):
-        path = os.fspath(path)
-        return path if os.path.splitext(path)[1] else path + ".zip"
 
     def save(self, path):
         """Everything a resumed run needs, as a zip of this project's own

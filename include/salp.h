@@ -381,6 +381,37 @@ typedef struct SalpPpoAdam {
 } SalpPpoAdam;
 #define SALP_PPO_APPLY_WORKSPACE_DOUBLES 256
 int salp_ppo_mlp_apply(const SalpPpoAdam* a, void* stream);
+/* One step of that policy on `rows` observations in one launch on the
+ * caller's stream (ActorCritic.act / .value, grasp_lab_salp_amd/ppo.py: predict,
+ * evaluate and the lock-step collection): mean = actor(obs),
+ * a = mean + exp(log_std) eps (eps NULL: a = mean, bit for bit; not clipped),
+ * log_prob = sum -(a - mean)^2 / (2 sigma^2) - log sigma - log sqrt(2 pi),
+ * value = critic(obs).  The actor is present when action is given, the critic
+ * when value is.  float32, in the operation order of salp_collect's in-kernel
+ * policy: on the same observations the values are the collection's, bit for
+ * bit.  A row's result depends on nothing but the row and the parameters (not
+ * on rows, its position, or the networks present).  No atomics, nothing
+ * allocated or synchronised; capturable in a HIP graph.  The parameter pointers
+ * are the torch tensors as they are.  Rows >= rows and outputs whose pointer is
+ * NULL are never written.  SALP_EINVAL before any launch for: a NULL struct,
+ * rows < 0, obs_dim outside 1 .. SALP_OBS_DIM_MAX, obs NULL, both networks
+ * absent, log_prob or eps without action, and a NULL tensor among those a
+ * present network needs (actor: PI_W1 .. LOG_STD; critic: VF_W1 .. VAL_B).
+ * rows == 0 is SALP_OK without a launch.  Added under ABI 14 without a new
+ * version number: a library built before it is recognised by the missing
+ * symbol.  No reference counterpart (its learners are stable-baselines3). */
+typedef struct SalpPpoMlpAct {
+    int64_t rows;
+    int32_t obs_dim;                           /* 1 .. SALP_OBS_DIM_MAX */
+    int32_t reserved;                          /* 0 */
+    const float* params[SALP_MLP_N_TENSORS];   /* the policy's own tensors, SalpMlpTensor order */
+    const float* obs;                          /* [rows][obs_dim] */
+    const float* eps;                          /* [rows][3] N(0,1); NULL: action = mean */
+    float* action;                             /* [rows][3] unclipped; NULL: actor absent */
+    float* log_prob;                           /* [rows] or NULL (needs action) */
+    float* value;                              /* [rows]; NULL: critic absent */
+} SalpPpoMlpAct;
+int salp_ppo_mlp_act(const SalpPpoMlpAct* a, void* stream);
 
 /* The LSTM cell of RecurrentPPO's MlpLstmPolicy (sb3-contrib RecurrentPPO,
  * src/train_robot_recurrent_ppo.py:85-107; grasp_lab_salp_amd/recurrent_ppo.py),

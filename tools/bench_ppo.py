@@ -30,6 +30,18 @@ on, ...); env-steps/s and the collect / GAE / update seconds of every
 iteration (HIP events) are printed as one JSON line and written to OUT.json.
 --collect-only K: K lock-step env-steps of one collection and nothing else
 (for a kernel trace: the launches per env-step are the difference of two K).
+
+    python tools/bench_ppo.py --ab-fused-act OUT.json [--iters 2]
+    python tools/bench_ppo.py --collect-only K --n-envs 4 [--fused-act]
+
+--ab-fused-act: lock-step PPO (collect="lockstep", n_steps 64) at 4, 1 024 and
+32 768 envs, two learners per size in this one process, fused_act off and on
+(the policy step as torch ops / as salp_ppo_mlp_act), one warm-up iteration
+each and then --iters timed iterations each in turn (off, on, off, on); the
+means of the collection's seconds per iteration (HIP events) and of env-steps/s
+(wall), and the wall time of evaluate(SalpVecEnv(5), 5) off and on, are printed
+as one JSON line and written to OUT.json.  --collect-only without --recurrent:
+one lock-step PPO collection of K env-steps (--fused-act: with the kernel).
 """
 import argparse
 import json
@@ -115,6 +127,66 @@ def recurrent_ab(a):
     print(json.dumps({k: res[k] for k in ("metric", "n_envs", "n_steps", "off", "on")}), flush=True)
 
 
+def ppo_act_ab(a):
+    """--ab-fused-act / --collect-only without --recurrent (see the module docstring); one GPU."""
+    from grasp_lab_salp_amd.ppo import PPO
+    from grasp_lab_salp_amd.vec_env import SalpVecEnv
+
+    def make(n_envs, n_steps, fused):
+        env = SalpVecEnv(n_envs, seed=0, infos=False)
+        return PPO("MlpPolicy", env, n_steps=n_steps, batch_size=min(n_envs * n_steps, 32768), n_epochs=2, seed=0,
+                   collect="lockstep", fused_act=fused)
+    if a.collect_only:
+        m = make(a.n_envs, a.collect_only, a.fused_act)
+        m.collect_rollouts()
+        torch.cuda.synchronize()
+        print(json.dumps({"collect_only_steps": a.collect_only, "n_envs": a.n_envs, "fused_act": a.fused_act}),
+              flush=True)
+        return
+    n_steps = 64
+    res = {"metric": "lock-step PPO iteration, fused_act off / on in turn (one process)", "n_steps": n_steps,
+           "n_epochs": 2, "iters": a.iters, "sizes": {}}
+    for n_envs in (4, 1024, 32768):
+        per_iter = n_steps * n_envs
+        models = {"off": make(n_envs, n_steps, False), "on": make(n_envs, n_steps, True)}
+        rows = []
+        for r in range(a.iters + 1):       # round 0: warm-up (graph capture, allocator)
+            for name, m in models.items():
+                before = dict(m.timing)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                m.learn(m.num_timesteps + per_iter)
+                torch.cuda.synchronize()
+                el = time.perf_counter() - t0
+                row = {"fused_act": name, "round": r, "warmup": r == 0, "wall_s": el, "env_steps_per_s": per_iter / el,
+                       **{k: m.timing[k] - before[k] for k in m.timing}}
+                rows.append(row)
+                print(json.dumps({"n_envs": n_envs, **row}), file=sys.stderr, flush=True)
+        size = {"iterations": rows}
+        for name in models:
+            timed = [x for x in rows if x["fused_act"] == name and not x["warmup"]]
+            size[name] = {k: sum(x[k] for x in timed) / len(timed) for k in ("env_steps_per_s", "collect_s", "gae_s",
+                                                                             "train_s", "wall_s")}
+        if n_envs == 4:     # evaluate(SalpVecEnv(5), 5): a warm-up run, then the timed ones in turn
+            ev = {name: [] for name in models}
+            for r in range(a.iters + 1):
+                for name, m in models.items():
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    m.evaluate(SalpVecEnv(5, seed=1), 5)
+                    if r:
+                        ev[name].append(time.perf_counter() - t0)
+            res["evaluate_wall_s"] = {name: sum(v) / len(v) for name, v in ev.items()}
+            res["evaluate_steps"] = max(models["on"].last_eval["lengths"])
+        res["sizes"][str(n_envs)] = size
+        del models
+        torch.cuda.empty_cache()
+    with open(a.ab_fused_act, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps({"metric": res["metric"], "evaluate_wall_s": res["evaluate_wall_s"],
+                      **{n: {k: v[k] for k in ("off", "on")} for n, v in res["sizes"].items()}}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n-envs", type=int, default=32768)
@@ -137,9 +209,13 @@ def main():
                     help="src/train_robot_recurrent_ppo.py:85-107: 4 envs, n_steps 2048, batch_size 64, seq_len 16")
     ap.add_argument("--ab-fused-step", metavar="OUT.json", help="fused_step off / on in turn in one process")
     ap.add_argument("--collect-only", type=int, default=0, metavar="K", help="one collection of K env-steps, no update")
+    ap.add_argument("--fused-act", action="store_true", help="PPO(fused_act=True) (with --collect-only)")
+    ap.add_argument("--ab-fused-act", metavar="OUT.json", help="lock-step PPO, fused_act off / on in turn in one process")
     a = ap.parse_args()
     if a.reference_config:
         a.n_envs, a.n_steps, a.batch_size, a.seq_len, a.recurrent = 4, 2048, 64, 16, True
+    if a.ab_fused_act or (a.collect_only and not a.recurrent):
+        return ppo_act_ab(a)
     if a.ab_fused_step or a.collect_only:
         return recurrent_ab(a)
     world = int(os.environ.get("WORLD_SIZE", "1"))

@@ -8,7 +8,7 @@ import ctypes
 
 ABI_VERSION = 14
 # rows of salp_math_selftest's output (include/salp.h)
-MATH_SELFTEST_ROWS = 23
+MATH_SELFTEST_ROWS = 24
 MAX_OBSTACLES = 4
 OBS_DIM_MAX = 6 + 2 * MAX_OBSTACLES
 

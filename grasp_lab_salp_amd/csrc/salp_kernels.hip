@@ -458,18 +458,10 @@ __device__ __forceinline__ float policy_value(PolicyW w, const float* x) {
 }
 
 // Three standard normals (Box-Muller on one Philox draw) for the exploration
-// noise of env `env_id` at its env-step `step`.
-#define SP_STREAM_POLICY 7u
+// noise of env `env_id` at its env-step `step`: sr_policy_noise (salp_random.h),
+// shared with the CPU oracle.
 __device__ __forceinline__ void policy_noise(uint64_t seed, uint64_t env_id, uint64_t step, float z[3]) {
-    const sp_u32x4 r = sp_draw(seed, env_id, step, SP_STREAM_POLICY, 0);
-    const double u1 = ((double)r.v[0] + 1.0) * 0x1.0p-32, u3 = ((double)r.v[2] + 1.0) * 0x1.0p-32;
-    const double rad1 = sqrt(-2.0 * sm_log(u1)), rad2 = sqrt(-2.0 * sm_log(u3));
-    double s1, c1, s2, c2;
-    sm_sincos(6.283185307179586 * sp_u01_32(r.v[1]), &s1, &c1);
-    sm_sincos(6.283185307179586 * sp_u01_32(r.v[3]), &s2, &c2);
-    z[0] = (float)(rad1 * c1);
-    z[1] = (float)(rad1 * s1);
-    z[2] = (float)(rad2 * c2);
+    sr_policy_noise(seed, env_id, step, z);
 }
 
 // The env's action for observation o: a = mean + std z (unclipped, as SB3's
@@ -2356,6 +2348,7 @@ __global__ void k_math_selftest(const double* x, const double* y, int64_t n, dou
     out[20 * n + i] = wf[2];
     out[21 * n + i] = sm_atan(x[i]);
     out[22 * n + i] = sm_atan_ref(x[i]);
+    out[23 * n + i] = sm_log(x[i]);
 }
 
 const char* const kFieldNames[SALP_NUM_FIELDS] = {

@@ -85,6 +85,7 @@ SP_QUAL void sp_reset_pair(uint64_t seed, uint64_t env_id, uint64_t episode, uin
 #define SP_STREAM_ACTNOISE 4u  /* SalpRobotEnv._randomize_actions, per env-step   */
 #define SP_STREAM_OBSNOISE 5u  /* SalpRobotEnv._randomize_observations, per step  */
 #define SP_STREAM_LATENCY 6u   /* the latency set_control's coast time, per step  */
+#define SP_STREAM_POLICY 7u    /* salp_collect's exploration noise, per env-step    */
 
 SP_QUAL sp_u32x4 sp_draw(uint64_t seed, uint64_t env_id, uint64_t ctr, uint32_t stream, uint32_t group) {
     return sp_philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), (uint32_t)env_id,

@@ -6,7 +6,8 @@
 // The arithmetic restates the in-kernel policy of salp_collect
 // (salp_kernels.hip policy_layer1 / policy_mlp / policy_act) operation for
 // operation, so that what evaluates a policy is, bit for bit, the function that
-// collected its data (tests/test_gpu_ppo_act.py):
+// collected its data (tests/test_gpu_ppo_act.py; every action, log-prob and
+// value of a collection: tests/test_gpu_collect_policy.py):
 //   layer 1   acc = b1[j]; acc = fma(W1[j][k], x[k], acc), k ascending over the
 //             SALP_OBS_DIM_MAX zero-padded inputs; salp_tanhf
 //   layer 2   even-k products summed from b2[j], odd-k products from 0, each

@@ -103,6 +103,29 @@ SR_QUAL void sr_normals3(uint64_t seed, uint64_t env_id, uint64_t ctr, double* n
     (void)s2;
 }
 
+/* The exploration noise of salp_collect's in-kernel policy (salp_kernels.hip
+ * policy_act): three float32 standard normals, Box-Muller on the four words of
+ * one Philox draw.  Words 0 and 2 give the radii through u = (w + 1) 2^-32 in
+ * (0, 1], words 1 and 3 the angles 2 pi w 2^-32; the second pair's sine is not
+ * used.  |z| <= sqrt(64 ln 2).  Pinned by tests/test_policy_noise.py. */
+SR_QUAL void sr_policy_noise_from_words(const uint32_t w[4], float z[3]) {
+    const double u1 = ((double)w[0] + 1.0) * 0x1.0p-32, u3 = ((double)w[2] + 1.0) * 0x1.0p-32;
+    const double rad1 = sqrt(-2.0 * sm_log(u1)), rad2 = sqrt(-2.0 * sm_log(u3));
+    double s1, c1, s2, c2;
+    sm_sincos(6.283185307179586 * sp_u01_32(w[1]), &s1, &c1);
+    sm_sincos(6.283185307179586 * sp_u01_32(w[3]), &s2, &c2);
+    z[0] = (float)(rad1 * c1);
+    z[1] = (float)(rad1 * s1);
+    z[2] = (float)(rad2 * c2);
+}
+/* ... of env `env_id` (global id) at its env-step `step` (the env's lifetime
+ * step counter, SALP_F_STEP_COUNT): stream SP_STREAM_POLICY, group 0, keyed by
+ * the collection's noise_seed. */
+SR_QUAL void sr_policy_noise(uint64_t seed, uint64_t env_id, uint64_t step, float z[3]) {
+    const sp_u32x4 r = sp_draw(seed, env_id, step, SP_STREAM_POLICY, 0);
+    sr_policy_noise_from_words(r.v, z);
+}
+
 /* OUDisturbance.sample, one component (mu = 0, dt = 0.01):
  * x + (theta * (mu - x) * dt + sigma * sqrt(dt) * n). */
 SR_QUAL double sr_ou_step(double x, double theta, double sigma, double n) {

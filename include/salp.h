@@ -867,9 +867,10 @@ int64_t salp_state_ptr(SalpEnv* h);
  * tick's shared-reciprocal division, 12-13 sin and cos of the tick's yaw
  * function, 14-17 sin x, cos x, sin y, cos y of the tick's roll / pitch pair
  * function at (x, y), 18-20 the tick's world-frame rotation of (y, x, 1) by
- * the angles (x, y, x + y), 21 atan (select form), 22 atan (fdlibm's branches)},
+ * the angles (x, y, x + y), 21 atan (select form), 22 atan (fdlibm's branches),
+ * 23 log (under the Box-Muller draws of the disturbance and policy noise)},
  * x, y [n]; out [SALP_MATH_SELFTEST_ROWS][n]. */
-#define SALP_MATH_SELFTEST_ROWS 23
+#define SALP_MATH_SELFTEST_ROWS 24
 int salp_math_selftest(const double* x, const double* y, int64_t n, double* out, void* stream);
 
 /* State fields.  Names follow the reference attribute they hold. */

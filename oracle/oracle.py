@@ -66,6 +66,9 @@ def lib(exact=False):
         L.oracle_robot_set_control.argtypes = [sp, i64, P(d), P(d), ctypes.c_int, ctypes.c_uint64, i64]
         L.oracle_robot_cycle.argtypes = [sp, i64, P(d), P(d), i64, P(i64), P(i64), ctypes.c_uint64, i64]
         L.oracle_philox.argtypes = [u32] * 6 + [P(u32)]
+        u64 = ctypes.c_uint64
+        L.oracle_policy_noise.argtypes = [u64, P(u64), i64, P(u64), i64, P(f)]
+        L.oracle_policy_noise_from_words.argtypes = [P(u32), i64, P(f)]
         if L.oracle_num_fields() != NUM_FIELDS:
             raise RuntimeError("oracle / _abi field count mismatch")
         _libs[exact] = L
@@ -248,6 +251,26 @@ def math_selftest(x, y, exact=False):
     out = np.zeros((MATH_SELFTEST_ROWS, len(x)), np.float64)
     lib(exact).oracle_math_selftest(_p(x, ctypes.c_double), _p(y, ctypes.c_double), len(x),
                                _p(out, ctypes.c_double))
+    return out
+
+
+def policy_noise(noise_seed, env_ids, steps):
+    """salp_collect's exploration noise (salp_random.h sr_policy_noise) for the
+    global env ids and the envs' lifetime step counters given: float32
+    [len(env_ids), len(steps), 3]."""
+    ids = np.ascontiguousarray([int(i) for i in env_ids], np.uint64)
+    st = np.ascontiguousarray([int(s) for s in steps], np.uint64)
+    out = np.zeros((len(ids), len(st), 3), np.float32)
+    lib().oracle_policy_noise(int(noise_seed) & (2 ** 64 - 1), _p(ids, ctypes.c_uint64), len(ids),
+                              _p(st, ctypes.c_uint64), len(st), _p(out, ctypes.c_float))
+    return out
+
+
+def policy_noise_from_words(words):
+    """The same Box-Muller on given Philox words: uint32 [n, 4] -> float32 [n, 3]."""
+    w = np.ascontiguousarray(words, np.uint32).reshape(-1, 4)
+    out = np.zeros((len(w), 3), np.float32)
+    lib().oracle_policy_noise_from_words(_p(w, ctypes.c_uint32), len(w), _p(out, ctypes.c_float))
     return out
 
 

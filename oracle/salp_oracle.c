@@ -1665,6 +1665,7 @@ void oracle_math_selftest(const double* x, const double* y, int64_t n, double* o
         out[20 * n + i] = wf[2];
         out[21 * n + i] = sm_atan(x[i]);
         out[22 * n + i] = sm_atan_ref(x[i]);
+        out[23 * n + i] = sm_log(x[i]);
     }
 }
 
@@ -1672,4 +1673,18 @@ void oracle_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t 
                    uint32_t* out) {
     sp_u32x4 r = sp_philox4x32_10(c0, c1, c2, c3, k0, k1);
     for (int i = 0; i < 4; ++i) out[i] = r.v[i];
+}
+
+/* The exploration noise of salp_collect's policy (salp_random.h
+ * sr_policy_noise): out [n_envs][n_steps][3] for the global env ids and the
+ * envs' lifetime step counters given. */
+void oracle_policy_noise(uint64_t noise_seed, const uint64_t* env_ids, int64_t n_envs, const uint64_t* steps,
+                         int64_t n_steps, float* out) {
+    for (int64_t i = 0; i < n_envs; ++i)
+        for (int64_t t = 0; t < n_steps; ++t) sr_policy_noise(noise_seed, env_ids[i], steps[t], out + (i * n_steps + t) * 3);
+}
+
+/* ... from the Philox words themselves: words [n][4], out [n][3]. */
+void oracle_policy_noise_from_words(const uint32_t* words, int64_t n, float* out) {
+    for (int64_t i = 0; i < n; ++i) sr_policy_noise_from_words(words + 4 * i, out + 3 * i);
 }

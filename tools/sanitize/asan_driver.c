@@ -47,6 +47,9 @@ int oracle_robot_set_control(const SalpParams* p, int64_t n, double* state, cons
 int oracle_robot_cycle(const SalpParams* p, int64_t n, double* state, double* rows, int64_t max_samples,
                        int64_t* n_samples, int64_t* ticks_out, uint64_t seed, int64_t env_offset);
 void oracle_math_selftest(const double* x, const double* y, int64_t n, double* out);
+void oracle_policy_noise(uint64_t noise_seed, const uint64_t* env_ids, int64_t n_envs, const uint64_t* steps,
+                         int64_t n_steps, float* out);
+void oracle_policy_noise_from_words(const uint32_t* words, int64_t n, float* out);
 
 #define CHECK(c)                                                         \
     do {                                                                 \
@@ -144,6 +147,14 @@ static void oracle_misc(void) {
     free(out);
     double x[5] = {0.0, -0.0, 1e-300, 3.0, -1e5}, y[5] = {1.0, -2.0, 0.0, INFINITY, 7.0}, m[SALP_MATH_SELFTEST_ROWS * 5];
     oracle_math_selftest(x, y, 5, m);
+    /* the collection's exploration noise: ids and steps on both sides of 2^32, the edge words */
+    const uint64_t ids[3] = {0, 0xFFFFFFFFull, 0x100000000ull}, steps[4] = {0, 1, 0xFFFFFFFFull, 0x100000005ull};
+    float z[3 * 4 * 3], zw[2 * 3];
+    oracle_policy_noise(0x100000063ull, ids, 3, steps, 4, z);
+    for (int i = 0; i < 36; ++i) CHECK(z[i] == z[i] && fabsf(z[i]) < 7.0f);
+    const uint32_t words[8] = {0u, 0u, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0x40000000u, 0u, 0x80000000u};
+    oracle_policy_noise_from_words(words, 2, zw);
+    CHECK(zw[1] == 0.0f && zw[3] == 0.0f && zw[4] == 0.0f);
 }
 
 static void abi_host_paths(void) {

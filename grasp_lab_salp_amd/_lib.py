@@ -304,6 +304,15 @@ class SalpEpisodePush(ctypes.Structure):
     ]
 
 
+class SalpEpisodeLog(ctypes.Structure):
+    _fields_ = [
+        ("per_env", ctypes.c_int64),
+        ("rows", ctypes.c_void_p),
+        ("step", ctypes.c_void_p),
+        ("count", ctypes.c_void_p),
+    ]
+
+
 class SalpEvalState(ctypes.Structure):
     _fields_ = [
         ("n_envs", ctypes.c_int64),
@@ -342,6 +351,7 @@ SIGNATURES = {
     "salp_rollout": (ctypes.c_int, [_H, ctypes.c_int64, ctypes.POINTER(SalpRolloutBuffers), _V]),
     "salp_step_random": (ctypes.c_int, [_H, ctypes.c_int32, _V, _V]),
     "salp_collect": (ctypes.c_int, [_H, ctypes.POINTER(SalpPolicyRollout), _V]),
+    "salp_collect_episodes": (ctypes.c_int, [_H, ctypes.POINTER(SalpPolicyRollout), ctypes.POINTER(SalpEpisodeLog), _V]),
     "salp_lstm_cell_forward": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, _V, _V, _V, _V, _V, _V, _V]),
     "salp_lstm_cell_backward": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
     "salp_lstm_step_forward": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int32, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
@@ -393,6 +403,8 @@ SIGNATURES = {
     "salp_sac_net_backward": (ctypes.c_int, [ctypes.POINTER(SalpSacNetBackward), _V]),
     "salp_episode_window_push": (ctypes.c_int, [ctypes.POINTER(SalpEpisodeWindow), ctypes.POINTER(SalpEpisodePush),
                                                 _V]),
+    "salp_episode_window_push_log": (ctypes.c_int, [ctypes.POINTER(SalpEpisodeWindow), ctypes.POINTER(SalpEpisodeLog),
+                                                    ctypes.c_int64, _V, _V]),
     "salp_episode_window_summary": (ctypes.c_int, [ctypes.POINTER(SalpEpisodeWindow), _V, _V]),
     "salp_eval_account": (ctypes.c_int, [ctypes.POINTER(SalpEvalState), ctypes.POINTER(SalpEpisodePush), _V]),
 }

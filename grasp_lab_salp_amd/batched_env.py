@@ -249,7 +249,7 @@ class BatchedSalpEnv:
         return steps_done
 
     def collect(self, weights, n_steps, buffers, episode_start, last_obs, ep_stats, diverged, noise_seed=0,
-                gamma=0.99, diverged_obs_abs=0.0, diverged_reward_abs=0.0):
+                gamma=0.99, diverged_obs_abs=0.0, diverged_reward_abs=0.0, episode_log=None):
         """Policy-in-the-loop collection (salp_collect): every env runs
         ``n_steps`` env-steps back to back with actions drawn by the packed
         MlpPolicy ``weights`` (:func:`ppo.pack_policy`) at its env-step
@@ -259,7 +259,9 @@ class BatchedSalpEnv:
         [n, obs_dim] in/out (in: the observation each env's first step is
         taken on, e.g. the one reset() returned), ``ep_stats`` [4] f64 (return, episodes,
         successes, length sums) and ``diverged`` [1] i64
-        accumulated.  See include/salp.h for the exact semantics."""
+        accumulated.  ``episode_log`` (a :class:`metrics.EpisodeLog` of this
+        env's size): also record every finished episode's window row
+        (salp_collect_episodes).  See include/salp.h for the exact semantics."""
         R = _lib.SalpPolicyRollout()
         w = weights
         if w.dtype != torch.float32 or w.numel() != POLICY_SIZE or not w.is_contiguous() or w.device != self.device:
@@ -285,7 +287,13 @@ class BatchedSalpEnv:
         R.gamma = float(gamma)
         R.diverged_obs_abs = float(diverged_obs_abs)
         R.diverged_reward_abs = float(diverged_reward_abs)
-        self._run(_lib.load().salp_collect(self._h, ctypes.byref(R), self._stream()))
+        if episode_log is None:
+            self._run(_lib.load().salp_collect(self._h, ctypes.byref(R), self._stream()))
+            return
+        if episode_log.n_envs != self.n_envs or episode_log.device != self.device:
+            raise ValueError(f"episode_log must hold {self.n_envs} envs on {self.device}")
+        self._run(_lib.load().salp_collect_episodes(self._h, ctypes.byref(R), ctypes.byref(episode_log.c_struct()),
+                                                    self._stream()))
 
     # ------------------------------------------- Robot / Nozzle level
     # The reference's bare-robot call sequence (src/compare_trajectories.py:

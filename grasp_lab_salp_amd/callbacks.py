@@ -31,15 +31,23 @@ and ``_on_steps(first, last)`` receives the 1-based numbers of the calls
 covered.  ``CheckpointCallback`` and ``EvalCallback`` then fire once if a
 multiple of their frequency lies in ``[first, last]``, under the current
 ``num_timesteps``.  A callback that overrides ``_on_step`` but not
-``_on_steps`` needs the per-step tensors (``DetailedMetricsCallback`` does):
-such a learner refuses it with ValueError when training starts; it runs under
-``collect="lockstep"``.
+``_on_steps`` needs the per-step tensors: such a learner refuses it with
+ValueError when training starts; it runs under ``collect="lockstep"``.
+
+``DetailedMetricsCallback`` runs on a chained learner built with
+``episode_log=True`` (or the largest window wanted): the collection kernels
+then record every finished episode's window row into a per-env log
+(``salp_collect_episodes``), ``locals`` is ``{"episode_log": log}``, and
+``_on_steps`` merges the log into the callback's window on the device in the
+order the per-step pushes would have used (``EpisodeWindow.push_log``).
+Without the log it is refused like any per-step callback.
 """
 import os
 
 import numpy as np
+import torch
 
-from .metrics import EpisodeWindow
+from .metrics import EpisodeWindow, summary_dict
 
 __all__ = ["BaseCallback", "CallbackList", "CheckpointCallback", "EvalCallback", "DetailedMetricsCallback",
            "evaluate_policy"]
@@ -81,7 +89,8 @@ class BaseCallback:
             if per_step:
                 raise ValueError(f"{', '.join(per_step)}: _on_step needs every env-step's tensors, and the chained "
                                  "collection has no env-step boundary on the host (callbacks run once per "
-                                 'collection, on_steps): build the learner with collect="lockstep"')
+                                 'collection, on_steps): build the learner with collect="lockstep" (or, for '
+                                 "DetailedMetricsCallback, with episode_log=True)")
         self._init_callback()
 
     def _init_callback(self):
@@ -110,7 +119,7 @@ class BaseCallback:
         first = self.n_calls + 1
         self.n_calls += int(k)
         self.num_timesteps = self.model.num_timesteps
-        self.locals = {}
+        self.locals = self.model.locals   # {} unless the learner logs episodes in its kernels ("episode_log")
         return bool(self._on_steps(first, self.n_calls))
 
     def _on_steps(self, first, last):
@@ -169,6 +178,9 @@ class CallbackList(BaseCallback):
         return go_on
 
     def per_step_only(self):
+        for cb in self.callbacks:   # asked before _init_callback: a member may need the learner to answer
+            if cb.model is None:
+                cb.model = self.model
         return [name for cb in self.callbacks for name in cb.per_step_only()]
 
     def _on_training_end(self):
@@ -330,7 +342,16 @@ class DetailedMetricsCallback(BaseCallback):
         self.window = None
         self.last_summary = None
 
+    def per_step_only(self):
+        """On a chained learner the window is fed from the learner's in-kernel
+        episode log; without one this callback needs every env-step."""
+        return [] if getattr(self.model, "episode_log", 0) else [type(self).__name__]
+
     def _init_callback(self):
+        w = getattr(self.model, "episode_log", 0)
+        if getattr(self.model, "collect", None) == "chained" and self.window_size > w:
+            raise ValueError(f"DetailedMetricsCallback(window={self.window_size}): the learner's episode log is sized "
+                             f"for windows up to {w}; build it with episode_log={self.window_size}")
         if self.window is None or self.window.device != self.model.device:
             fused = getattr(self.model, "fused", None) if self.fused is None else self.fused
             self.window = EpisodeWindow(self.window_size, self.model.device, fused=fused)
@@ -341,11 +362,26 @@ class DetailedMetricsCallback(BaseCallback):
         if self.n_calls % self.log_freq == 0:
             s = self.window.summary()
             if s["n"] > 0:
-                self.last_summary = s
-                for key, name in _SUMMARY_KEYS:
-                    if name == "cycles_to_success" and s["n_success"] == 0:
-                        continue
-                    self.logger.record(key, s[name])
+                self._record(s)
+        return True
+
+    def _record(self, s):
+        self.last_summary = s
+        for key, name in _SUMMARY_KEYS:
+            if name == "cycles_to_success" and s["n_success"] == 0:
+                continue
+            self.logger.record(key, s[name])
+
+    def _on_steps(self, first, last):
+        self.window.push_log(self.locals["episode_log"])
+        if self._due(self.log_freq, first, last):
+            # one host copy for the summary and the lost counter together
+            host = torch.cat([self.window.summary_tensor(), self.window.lost.to(torch.float64)]).tolist()
+            s, lost = summary_dict(host[:-1]), int(host[-1])
+            if s["n"] > 0:
+                self._record(s)
+            if lost:
+                self.logger.record("custom/episodes_lost", lost)
         return True
 
 

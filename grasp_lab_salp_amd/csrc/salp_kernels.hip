@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 
 #include "salp_device.h"
 #include "salp_host.h"
@@ -536,12 +537,18 @@ __device__ __forceinline__ float clamp_box(float a, float lo, float hi) { return
 // is cut into launches and chunks changes nothing but the count of env-steps
 // a launch completes.  POL: the actions come from the policy of salp_collect
 // and the outputs go to its buffers (R).
-template <bool RAND, bool POL, class ST, class VS = ValuesInPlace>
+// LOG (salp_collect_episodes): every episode that updates ep_stats also writes
+// its window row into the env's own slots of L (no atomics: the lane owns the
+// env for the launch; the re-seat hands count[i] on like the cold state, behind
+// the workgroup barrier).  Without LOG nothing of it is compiled.
+template <bool RAND, bool POL, bool LOG = false, class ST, class VS = ValuesInPlace>
 __device__ __forceinline__ void rollout_boundary(Hot& h, ST S, const Params& P, int64_t i,
                                                  uint64_t env_id, bool& pending, bool& active,
                                                  int64_t& steps, int64_t max_steps,
                                                  const SalpRolloutBuffers& B, double* reward_sum,
-                                                 const SalpPolicyRollout& R, salp::Cache32 c32, VS vs = VS()) {
+                                                 const SalpPolicyRollout& R, salp::Cache32 c32, VS vs = VS(),
+                                                 const SalpEpisodeLog& L = SalpEpisodeLog{}) {
+    static_assert(!LOG || POL, "the episode log belongs to salp_collect_episodes");
     // o: the env's current observation once this boundary has produced one
     // (after a finished step, or the reset obs after an episode end)
     float o[SALP_OBS_DIM_MAX];
@@ -553,7 +560,8 @@ __device__ __forceinline__ void rollout_boundary(Hot& h, ST S, const Params& P, 
         vs.start_rep();
         if (fin) {
             SF(SALP_F_STEP_COUNT) = SF(SALP_F_STEP_COUNT) + 1.0;
-            salp::StepOut r = salp::finish_step<RAND>(h, S, P, i, o, nullptr);
+            double info[LOG ? SALP_INFO_DIM : 1];
+            salp::StepOut r = salp::finish_step<RAND>(h, S, P, i, o, LOG ? info : nullptr);
             bool reset = r.terminated || r.truncated;
             if (POL) {
                 // SB3 collect_rollouts + the learner's divergence guard (ppo.py):
@@ -582,6 +590,20 @@ __device__ __forceinline__ void rollout_boundary(Hot& h, ST S, const Params& P, 
                     atomicAdd(&R.ep_stats[1], 1.0);
                     if (r.terminated) atomicAdd(&R.ep_stats[2], 1.0);   // the target was reached
                     atomicAdd(&R.ep_stats[3], SF(SALP_F_EP_LEN));
+                    if constexpr (LOG) {
+                        // the env's e-th episode of the call into slot e % K, as k_epwin_push lays a row out
+                        const int32_t e = L.count[i];
+                        const size_t slot = (size_t)i * (size_t)L.per_env + (size_t)((int64_t)e % L.per_env);
+                        long long* dst = reinterpret_cast<long long*>(L.rows) + slot * SALP_EPWIN_COLS;
+                        dst[0] = __double_as_longlong(info[SALP_INFO_EP_RETURN]);
+                        dst[1] = __double_as_longlong(info[SALP_INFO_EP_LEN]);
+                        dst[2] = __double_as_longlong(r.terminated ? 1.0 : 0.0);
+                        dst[3] = __double_as_longlong(r.terminated ? 0.0 : 1.0);   // reset: truncated if not terminated
+                        for (int k = 0; k < SALP_EPWIN_COLS - 4; ++k)
+                            dst[4 + k] = __double_as_longlong(info[SALP_INFO_PATH_LENGTH + k]);
+                        L.step[slot] = (int32_t)steps;
+                        L.count[i] = e + 1;
+                    }
                 }
                 if (!(VS::kDefer && !bad && r.truncated && !r.terminated)) R.rewards[row] = rew;
                 reset = reset || bad;
@@ -696,6 +718,16 @@ struct RolloutArgs {
     SalpPolicyRollout R;  // POL kernels (salp_collect)
 };
 static_assert(sizeof(RolloutArgs) % 8 == 0, "RolloutArgs is copied as 8-byte words");
+// The LOG kernels' arguments: RolloutArgs with the episode log behind it, so
+// every other kernel keeps its kernarg segment and wave_ticks reads the same
+// prefix of either.
+struct RolloutArgsLog : RolloutArgs {
+    SalpEpisodeLog L;
+};
+static_assert(sizeof(RolloutArgsLog) == sizeof(RolloutArgs) + sizeof(SalpEpisodeLog) && sizeof(SalpEpisodeLog) % 8 == 0,
+              "the log follows RolloutArgs in the kernarg segment");
+template <bool LOG>
+using ArgsOf = std::conditional_t<LOG, RolloutArgsLog, RolloutArgs>;
 typedef const __attribute__((address_space(4))) uint64_t* KernargWords;
 __device__ __forceinline__ RolloutArgs args_at(KernargWords p) {
     asm volatile("" : "+s"(p));   // opaque: the loads below stay where they are used
@@ -709,6 +741,19 @@ __device__ __forceinline__ RolloutArgs args_at(KernargWords p) {
 // call ABI does not pass it); a callee takes the address as an argument.
 __device__ __forceinline__ RolloutArgs fresh_args() {
     return args_at((KernargWords)__builtin_amdgcn_kernarg_segment_ptr());
+}
+// The log of a LOG kernel, re-read the same way (kernels only); empty without LOG.
+template <bool LOG>
+__device__ __forceinline__ SalpEpisodeLog fresh_log() {
+    SalpEpisodeLog l{};
+    if constexpr (LOG) {
+        KernargWords p = (KernargWords)__builtin_amdgcn_kernarg_segment_ptr() + sizeof(RolloutArgs) / 8;
+        asm volatile("" : "+s"(p));
+        uint64_t w[sizeof(SalpEpisodeLog) / 8];
+        for (size_t k = 0; k < sizeof(SalpEpisodeLog) / 8; ++k) w[k] = p[k];
+        __builtin_memcpy(&l, w, sizeof l);
+    }
+    return l;
 }
 
 // Env-step boundaries park the whole wave's tick state in LDS (SpillSlot),
@@ -781,16 +826,17 @@ __device__ __forceinline__ bool unsteady(const Hot& h, const Params& P, bool act
 // randomisation) keeps it inline: called, even without register saves, it
 // spills more (profiles/r8_experiments.md, r8-3).  The plain rollout
 // (k_rollout<false, false>, the bench path) runs role_boundary instead.
-template <bool RAND, bool POL>
+template <bool RAND, bool POL, bool LOG = false>
 __device__ __forceinline__ bool lane_boundary(const RolloutArgs& a, salp::SpillSlot sp, int64_t i, bool& pending,
-                                              bool& active, int64_t& steps, double* c32p) {
+                                              bool& active, int64_t& steps, double* c32p,
+                                              const SalpEpisodeLog& L = SalpEpisodeLog{}) {
     const uint64_t env_id = (uint64_t)(a.P.env_offset + i);
     salp::ColdRegs<RAND> C;
     salp::load_cold<RAND>(C, a.S, a.P, i);
     Hot hb;
     salp::unspill<RAND>(hb, sp, a.P, env_id);
-    rollout_boundary<RAND, POL>(hb, &C, a.P, i, env_id, pending, active, steps, a.max_steps, a.B,
-                                a.reward_sum, a.R, salp::Cache32{c32p});
+    rollout_boundary<RAND, POL, LOG>(hb, &C, a.P, i, env_id, pending, active, steps, a.max_steps, a.B,
+                                     a.reward_sum, a.R, salp::Cache32{c32p}, ValuesInPlace(), L);
     salp::store_cold<RAND>(C, a.S, a.P, i);
     salp::spill<RAND>(hb, sp);
     return unsteady(hb, a.P, active);
@@ -799,6 +845,12 @@ template <bool RAND, bool POL>
 __device__ __noinline__ bool lane_boundary_call(const RolloutArgs* a, double* spp, int64_t i, bool* pending,
                                                 bool* active, int64_t* steps, double* c32p) {
     return lane_boundary<RAND, POL>(*a, salp::SpillSlot{spp}, i, *pending, *active, *steps, c32p);
+}
+// ... of the LOG kernel: a function of its own, so the one above keeps its symbol and code
+template <bool RAND>
+__device__ __noinline__ bool lane_boundary_call_log(const RolloutArgsLog* a, double* spp, int64_t i, bool* pending,
+                                                    bool* active, int64_t* steps, double* c32p) {
+    return lane_boundary<RAND, true, true>(*a, salp::SpillSlot{spp}, i, *pending, *active, *steps, c32p, a->L);
 }
 
 // SALP_ROLLOUT_PROF=1 (experiment builds only, tools/rollout_phase_prof.py):
@@ -1237,8 +1289,8 @@ __device__ __forceinline__ void role_boundary(const RoleLds L, const int b, cons
 }
 
 
-template <bool RAND, bool POL>
-__global__ __launch_bounds__(kBlock) void k_rollout(RolloutArgs A) {
+template <bool RAND, bool POL, bool LOG>
+__device__ __forceinline__ void rollout_kernel(const ArgsOf<LOG>& A) {
     double* const S = A.S;
     const Params& P = A.P;
     const int64_t base = (int64_t)blockIdx.x * blockDim.x;
@@ -1299,10 +1351,13 @@ __global__ __launch_bounds__(kBlock) void k_rollout(RolloutArgs A) {
             if (last) steps = s_steps[s];
         } else if (need) {
             if (RAND) {
-                uns = lane_boundary_call<RAND, POL>(&A, s_spill + s, i, &pending, &active, &steps, s_cache32 + s);
+                if constexpr (LOG)
+                    uns = lane_boundary_call_log<RAND>(&A, s_spill + s, i, &pending, &active, &steps, s_cache32 + s);
+                else
+                    uns = lane_boundary_call<RAND, POL>(&A, s_spill + s, i, &pending, &active, &steps, s_cache32 + s);
             } else {
                 const RolloutArgs a = fresh_args();
-                uns = lane_boundary<RAND, POL>(a, sp, i, pending, active, steps, s_cache32 + s);
+                uns = lane_boundary<RAND, POL, LOG>(a, sp, i, pending, active, steps, s_cache32 + s, fresh_log<LOG>());
             }
         }
         if (last) {
@@ -1364,8 +1419,8 @@ __global__ __launch_bounds__(kBlock) void k_rollout(RolloutArgs A) {
     if (A.B.steps_done && i < P.n) A.B.steps_done[i] = steps;
 }
 #else
-template <bool RAND, bool POL>
-__global__ __launch_bounds__(kBlock) void k_rollout(RolloutArgs A) {
+template <bool RAND, bool POL, bool LOG>
+__device__ __forceinline__ void rollout_kernel(const ArgsOf<LOG>& A) {
     double* const S = A.S;
     const Params& P = A.P;
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1395,8 +1450,8 @@ __global__ __launch_bounds__(kBlock) void k_rollout(RolloutArgs A) {
                 salp::load_cold<RAND>(C, a.S, a.P, i);
                 Hot hb;
                 salp::unspill<RAND>(hb, sp, a.P, env_id);
-                rollout_boundary<RAND, POL>(hb, &C, a.P, i, env_id, pending, active, steps, a.max_steps, a.B,
-                                            a.reward_sum, a.R, c32);
+                rollout_boundary<RAND, POL, LOG>(hb, &C, a.P, i, env_id, pending, active, steps, a.max_steps, a.B,
+                                                 a.reward_sum, a.R, c32, ValuesInPlace(), fresh_log<LOG>());
                 salp::store_cold<RAND>(C, a.S, a.P, i);
                 salp::spill<RAND>(hb, sp);
             }
@@ -1417,6 +1472,18 @@ __global__ __launch_bounds__(kBlock) void k_rollout(RolloutArgs A) {
     if (A.B.steps_done) A.B.steps_done[i] = steps;
 }
 #endif
+
+// The kernels of the body above.  The episode log has kernels of its own
+// (k_rollout_log and, below, k_rollout_pair_log / k_rollout_split_log), so
+// the ones without it keep their symbols, arguments and code.
+template <bool RAND, bool POL>
+__global__ __launch_bounds__(kBlock) void k_rollout(RolloutArgs A) {
+    rollout_kernel<RAND, POL, false>(A);
+}
+template <bool RAND>
+__global__ __launch_bounds__(kBlock) void k_rollout_log(RolloutArgsLog A) {
+    rollout_kernel<RAND, true, true>(A);
+}
 
 // ----------------------------------------------------------------------
 // k_rollout_pair: the chained rollout with every env on TWO waves
@@ -1798,7 +1865,7 @@ constexpr int kSplitEnd = 1 << 30;       // the A wave's counter: end of its chu
 static_assert(2 * kSplitRing * 6 * 64 <= salp::SPILL_N * kPairEnvs, "the rings live in the spill slots' LDS");
 constexpr int kSplitParts = salp::TD_FORCES | salp::TD_POSITIONS;
 
-template <bool POL, bool SPLIT = false>
+template <bool POL, bool SPLIT = false, bool LOG = false>
 __device__ __forceinline__ void pair_wave_a(PairShared& sh, PairJobs* jobs, const RolloutArgs& A, int grp, int lane) {
     const Params& P = A.P;
     const int seat = grp * 64 + lane;
@@ -1851,9 +1918,9 @@ __device__ __forceinline__ void pair_wave_a(PairShared& sh, PairJobs* jobs, cons
             Hot hb;
             salp::unspill<false>(hb, sl, a.P, env_id);
             if (POL)
-                rollout_boundary<false, POL>(hb, &C, a.P, i, env_id, pending, active, steps, a.max_steps, a.B,
-                                             a.reward_sum, a.R, salp::Cache32{sh.cache32 + s, kPairEnvs},
-                                             ValuesToPartner{jobs, grp, s, 0});
+                rollout_boundary<false, POL, LOG>(hb, &C, a.P, i, env_id, pending, active, steps, a.max_steps, a.B,
+                                                  a.reward_sum, a.R, salp::Cache32{sh.cache32 + s, kPairEnvs},
+                                                  ValuesToPartner{jobs, grp, s, 0}, fresh_log<LOG>());
             else
                 rollout_boundary<false, POL>(hb, &C, a.P, i, env_id, pending, active, steps, a.max_steps, a.B,
                                              a.reward_sum, a.R, salp::Cache32{sh.cache32 + s, kPairEnvs});
@@ -2196,8 +2263,8 @@ __device__ __forceinline__ PairJobs* pair_jobs_lds() {
 template <>
 __device__ __forceinline__ PairJobs* pair_jobs_lds<false>() { return nullptr; }
 
-template <bool POL>
-__global__ __launch_bounds__(kBlock) void k_rollout_pair(RolloutArgs A) {
+template <bool POL, bool SPLIT, bool LOG>
+__device__ __forceinline__ void pair_kernel(const ArgsOf<LOG>& A) {
     __shared__ PairShared sh;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane = (int)(threadIdx.x & 63);
@@ -2207,26 +2274,22 @@ __global__ __launch_bounds__(kBlock) void k_rollout_pair(RolloutArgs A) {
         for (int k = (int)threadIdx.x; k < kPolL2; k += kBlock) jobs->pi_l2[k] = src[k];
         __syncthreads();
     }
-    if (wave & 1) pair_wave_b<POL>(sh, jobs, A, wave >> 1, lane);
-    else pair_wave_a<POL>(sh, jobs, A, wave >> 1, lane);
+    if (wave & 1) pair_wave_b<POL, SPLIT>(sh, jobs, A, wave >> 1, lane);
+    else pair_wave_a<POL, SPLIT, LOG>(sh, jobs, A, wave >> 1, lane);
 }
+template <bool POL>
+__global__ __launch_bounds__(kBlock) void k_rollout_pair(RolloutArgs A) {
+    pair_kernel<POL, false, false>(A);
+}
+__global__ __launch_bounds__(kBlock) void k_rollout_pair_log(RolloutArgsLog A) { pair_kernel<true, false, true>(A); }
 
 // k_rollout_split: k_rollout_pair's workgroup with the tick split one way
 // (pair_wave_a / pair_wave_b, SPLIT).
 template <bool POL>
 __global__ __launch_bounds__(kBlock) void k_rollout_split(RolloutArgs A) {
-    __shared__ PairShared sh;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int lane = (int)(threadIdx.x & 63);
-    PairJobs* const jobs = pair_jobs_lds<POL>();
-    if (POL) {   /* the actor's second layer into LDS, once per workgroup */
-        const float* src = (const float*)A.R.weights + SALP_POLICY_PI_W2;
-        for (int k = (int)threadIdx.x; k < kPolL2; k += kBlock) jobs->pi_l2[k] = src[k];
-        __syncthreads();
-    }
-    if (wave & 1) pair_wave_b<POL, true>(sh, jobs, A, wave >> 1, lane);
-    else pair_wave_a<POL, true>(sh, jobs, A, wave >> 1, lane);
+    pair_kernel<POL, true, false>(A);
 }
+__global__ __launch_bounds__(kBlock) void k_rollout_split_log(RolloutArgsLog A) { pair_kernel<true, true, true>(A); }
 
 // The ABI's field-major state (state[f * n + i]) <-> the handle's layout
 // (field-major rows + env-major cold block, salp_device.h "state layout").
@@ -2515,7 +2578,24 @@ bool use_step_wave(const SalpEnv* h) {
 }
 
 // One chained launch on the kernel use_pair chooses.
-int launch_chained(SalpEnv* h, const RolloutArgs& args, bool pol, hipStream_t st, const char* what) {
+int launch_chained(SalpEnv* h, const RolloutArgs& args, bool pol, hipStream_t st, const char* what,
+                   const SalpEpisodeLog* log = nullptr) {
+    if (log) {   // salp_collect_episodes: the same choice of kernel, its LOG instance
+        RolloutArgsLog la{args, *log};
+        if (use_pair(h)) {
+            if (use_split(h)) {
+                la.steady_q8 = split_collect_steady_q8();
+                hipLaunchKernelGGL(k_rollout_split_log, dim3(pair_blocks_for(h->n)), dim3(kBlock), 0, st, la);
+            } else {
+                la.steady_q8 = pair_collect_steady_q8();
+                hipLaunchKernelGGL(k_rollout_pair_log, dim3(pair_blocks_for(h->n)), dim3(kBlock), 0, st, la);
+            }
+        } else {
+            hipLaunchKernelGGL((randomized(h->dp) ? k_rollout_log<true> : k_rollout_log<false>),
+                               dim3(blocks_for(h->n)), dim3(kBlock), 0, st, la);
+        }
+        return launched(h, what);
+    }
     if (use_pair(h)) {
         RolloutArgs pa = args;
         if (use_split(h)) {
@@ -2786,6 +2866,10 @@ int salp_rollout(SalpEnv* h, int64_t tick_budget, const SalpRolloutBuffers* buf,
 }
 
 int salp_collect(SalpEnv* h, const SalpPolicyRollout* r, void* stream) {
+    return salp_collect_episodes(h, r, nullptr, stream);
+}
+
+int salp_collect_episodes(SalpEnv* h, const SalpPolicyRollout* r, const SalpEpisodeLog* log, void* stream) {
     if (!h) return fail(nullptr, SALP_EINVAL, "salp_collect: null handle");
     if (!r || !r->weights || r->n_steps <= 0)
         return fail(h, SALP_EINVAL, "salp_collect: weights and n_steps > 0 are required");
@@ -2793,8 +2877,13 @@ int salp_collect(SalpEnv* h, const SalpPolicyRollout* r, void* stream) {
         !r->episode_start || !r->last_obs || !r->ep_stats || !r->diverged)
         return fail(h, SALP_EINVAL, "salp_collect: every buffer is required");
     if (r->n_steps > (int64_t)1 << 24) return fail(h, SALP_EINVAL, "salp_collect: n_steps too large");
+    if (log && log->per_env < 1) return fail(h, SALP_EINVAL, "salp_collect_episodes: per_env must be >= 1");
+    if (log && (!log->rows || !log->step || !log->count))
+        return fail(h, SALP_EINVAL, "salp_collect_episodes: rows, step and count are required");
     hipStream_t st = (hipStream_t)stream;
     int rc = check_hip(h, hipMemsetAsync(h->step_counts, 0, sizeof(int64_t) * h->n, st), "salp_collect memset");
+    // count is this call's alone: the kernel counts each env's episodes up from zero
+    if (!rc && log) rc = check_hip(h, hipMemsetAsync(log->count, 0, sizeof(int32_t) * h->n, st), "salp_collect memset");
     if (rc) return rc;
     SalpRolloutBuffers b{};
     b.steps_done = h->step_counts;
@@ -2816,7 +2905,7 @@ int salp_collect(SalpEnv* h, const SalpPolicyRollout* r, void* stream) {
     const int32_t chunk = forced_chunk ? forced_chunk : use_pair(h) ? 176 : 384;
     const int64_t n_chunks = (r->n_steps * kMaxTicksPerCycle + chunk - 1) / chunk;
     RolloutArgs args{h->state, h->dp, n_chunks, chunk, rollout_steady_q8(), r->n_steps, b, nullptr, 1, 0, *r};
-    return launch_chained(h, args, true, st, "k_rollout(collect)");
+    return launch_chained(h, args, true, st, "k_rollout(collect)", log);
 }
 
 int salp_robot_reset(SalpEnv* h, const uint8_t* mask, void* stream) {

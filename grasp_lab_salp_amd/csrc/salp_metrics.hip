@@ -102,6 +102,123 @@ __global__ __launch_bounds__(kPushBlock) void k_epwin_push(SalpEpisodeWindow w, 
     if (threadIdx.x == 0) w.count[0] = count0 + D;
 }
 
+// ---------------------------------------------------------------- k_epwin_push_log
+// One salp_collect_episodes log into the window, in the order the lock-step
+// pushes would have used: by (step, env).  A candidate is a kept slot of an
+// env's ring; its key is step * n_envs + env, and keys are distinct (an env
+// ends at most one episode per step).
+struct LogCand {
+    bool kept;
+    bool oldest_of_dropper;   // the env dropped episodes and this is the oldest it kept
+    int64_t key;
+};
+__device__ __forceinline__ LogCand log_candidate(const SalpEpisodeLog& l, int64_t n_envs, int64_t idx) {
+    const int64_t K = l.per_env;
+    // most logs have fewer than 2^32 slots: the 32-bit division is several times cheaper
+    const int64_t i = ((uint64_t)(n_envs * K) >> 32) == 0 ? (int64_t)((uint32_t)idx / (uint32_t)K) : idx / K;
+    const int64_t slot = idx - i * K;
+    const int64_t cnt = l.count[i] > 0 ? l.count[i] : 0;
+    LogCand c{slot < cnt, false, 0};
+    if (c.kept) {
+        c.key = (int64_t)l.step[idx] * n_envs + i;
+        if (cnt > K) {   // the ring wrapped: slot holds the env's latest episode e with e % K == slot
+            int64_t e = (cnt - 1) / K * K + slot;
+            if (e > cnt - 1) e -= K;
+            c.oldest_of_dropper = e == cnt - K;
+        }
+    }
+    return c;
+}
+
+// The block's sum of v; every thread gets it.  One barrier: the caller alternates buf.
+__device__ __forceinline__ int64_t block_sum(int64_t v, int64_t* buf) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    if (threadIdx.x % 64 == 0) buf[threadIdx.x / 64] = v;
+    __syncthreads();
+    int64_t s = 0;
+    for (int k = 0; k < kPushWaves; ++k) s += buf[k];
+    return s;
+}
+
+// Pass 1: D (all episodes), M (kept ones) and the largest key.  Then a
+// bisection on the key finds the threshold T with exactly min(window, M) kept
+// keys >= T (one pass over the candidates per bit of the key range), the
+// selected candidates go to LDS (an integer counter hands out the places:
+// their order does not matter), and each is ranked against the others: with
+// g selected keys above it, it is episode count + D - 1 - g.
+__global__ __launch_bounds__(kPushBlock) void k_epwin_push_log(SalpEpisodeWindow w, SalpEpisodeLog l, int64_t n_envs,
+                                                               int64_t* lost) {
+    __shared__ int64_t tot[3][kPushWaves];
+    __shared__ int64_t s_key[SALP_EPWIN_MAX_WINDOW];
+    __shared__ int64_t s_loc[SALP_EPWIN_MAX_WINDOW];   // slot index, bit 62: oldest_of_dropper
+    __shared__ int s_n, s_lost;
+    const int64_t K = l.per_env, total = n_envs * K;
+    const int64_t count0 = w.count[0];
+    if (threadIdx.x == 0) s_n = s_lost = 0;
+
+    int64_t d = 0, m = 0, top = -1;
+    for (int64_t i = threadIdx.x; i < n_envs; i += kPushBlock) {
+        const int64_t cnt = l.count[i] > 0 ? l.count[i] : 0;
+        d += cnt;
+        m += cnt < K ? cnt : K;
+    }
+    for (int64_t idx = threadIdx.x; idx < total; idx += kPushBlock) {
+        const LogCand c = log_candidate(l, n_envs, idx);
+        if (c.kept && c.key > top) top = c.key;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const int64_t u = __shfl_xor(top, o, 64);
+        top = u > top ? u : top;
+    }
+    if (threadIdx.x % 64 == 0) tot[2][threadIdx.x / 64] = top;
+    const int64_t D = block_sum(d, tot[0]);
+    const int64_t M = block_sum(m, tot[1]);   // its barrier covers tot[2] and s_n too
+    for (int k = 0; k < kPushWaves; ++k) top = tot[2][k] > top ? tot[2][k] : top;
+    if (D == 0) return;   // uniform
+    const int64_t sel = M < w.window ? M : w.window;   // >= 1: an env with an episode keeps one
+
+    int64_t lo = 0, hi = top + 1;   // kept keys >= lo: at least sel; >= hi: fewer
+    for (int it = 0; hi - lo > 1; ++it) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        int64_t above = 0;
+        for (int64_t idx = threadIdx.x; idx < total; idx += kPushBlock) {
+            const LogCand c = log_candidate(l, n_envs, idx);
+            above += c.kept && c.key >= mid ? 1 : 0;
+        }
+        // tot[0] and tot[1] in turn: a buffer is written again two barriers after its reads
+        if (block_sum(above, tot[it & 1]) >= sel) lo = mid; else hi = mid;
+    }
+    for (int64_t idx = threadIdx.x; idx < total; idx += kPushBlock) {
+        const LogCand c = log_candidate(l, n_envs, idx);
+        if (c.kept && c.key >= lo) {
+            const int at = atomicAdd(&s_n, 1);   // integer, LDS: exactly sel of them
+            if (at < SALP_EPWIN_MAX_WINDOW) {
+                s_key[at] = c.key;
+                s_loc[at] = idx | (c.oldest_of_dropper ? (int64_t)1 << 62 : 0);
+            }
+        }
+    }
+    __syncthreads();
+    const int n_sel = s_n < SALP_EPWIN_MAX_WINDOW ? s_n : SALP_EPWIN_MAX_WINDOW;
+    if ((int)threadIdx.x < n_sel) {
+        const int64_t key = s_key[threadIdx.x];
+        int64_t g = 0;
+        for (int k = 0; k < n_sel; ++k) g += s_key[k] > key ? 1 : 0;
+        const int64_t ep = count0 + D - 1 - g;
+        const int64_t loc = s_loc[threadIdx.x];
+        if (loc >> 62) atomicAdd(&s_lost, 1);
+        const uint64_t* src = reinterpret_cast<const uint64_t*>(l.rows) + (loc & (((int64_t)1 << 62) - 1)) * SALP_EPWIN_COLS;
+        uint64_t* dst = reinterpret_cast<uint64_t*>(w.rows) + (ep % w.window) * SALP_EPWIN_COLS;
+        for (int k = 0; k < SALP_EPWIN_COLS; ++k) dst[k] = src[k];   // bit copies
+    }
+    __syncthreads();
+    // every thread read count[0] before the first barrier
+    if (threadIdx.x == 0) {
+        w.count[0] = count0 + D;
+        if (s_lost) lost[0] += s_lost;
+    }
+}
+
 // A wave's sum in one fixed order: each lane adds its rows in ascending order, then the butterfly.
 __device__ __forceinline__ double wave_sum(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -215,6 +332,20 @@ int salp_episode_window_push(const SalpEpisodeWindow* w, const SalpEpisodePush* 
         return fail(SALP_EINVAL, "salp_episode_window_push: n_envs >= 1 and info, terminated, truncated set");
     hipLaunchKernelGGL(k_epwin_push, dim3(1), dim3(kPushBlock), 0, (hipStream_t)stream, *w, *p);
     return check_hip(hipGetLastError(), "k_epwin_push");
+}
+
+int salp_episode_window_push_log(const SalpEpisodeWindow* w, const SalpEpisodeLog* log, int64_t n_envs,
+                                 int64_t* lost, void* stream) {
+    if (!epwin_ok(w))
+        return fail(SALP_EINVAL, "salp_episode_window_push_log: window must be in 1 .. 1024, rows and count set");
+    if (!log || log->per_env < 1 || n_envs < 1)
+        return fail(SALP_EINVAL, "salp_episode_window_push_log: a log, per_env >= 1 and n_envs >= 1 are required");
+    if (!log->rows || !log->step || !log->count || !lost)
+        return fail(SALP_EINVAL, "salp_episode_window_push_log: rows, step, count and lost must be set");
+    if (n_envs > INT64_MAX / ((int64_t)1 << 25) || log->per_env > INT64_MAX / ((int64_t)1 << 25) / n_envs)
+        return fail(SALP_EINVAL, "salp_episode_window_push_log: n_envs * per_env too large");
+    hipLaunchKernelGGL(k_epwin_push_log, dim3(1), dim3(kPushBlock), 0, (hipStream_t)stream, *w, *log, n_envs, lost);
+    return check_hip(hipGetLastError(), "k_epwin_push_log");
 }
 
 int salp_episode_window_summary(const SalpEpisodeWindow* w, double* out, void* stream) {

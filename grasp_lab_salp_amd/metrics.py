@@ -26,8 +26,9 @@ import torch
 from . import _lib
 from ._abi import INFO, INFO_DIM, INFO_KEYS
 
-__all__ = ["EpisodeWindow", "EvalAccount", "ROW_KEYS", "SUMMARY_STATS", "torch_episode_window_push",
-           "torch_episode_window_summary", "torch_eval_account", "eval_targets", "summary_dict"]
+__all__ = ["EpisodeWindow", "EpisodeLog", "EvalAccount", "ROW_KEYS", "SUMMARY_STATS", "torch_episode_window_push",
+           "torch_episode_window_push_log", "torch_episode_window_summary", "torch_eval_account", "eval_targets",
+           "summary_dict"]
 
 _FIRST, _LAST = INFO["path_length"], INFO["avg_rewards_obstacle"]
 # column names of a window row (include/salp.h SalpEpisodeWindow)
@@ -87,6 +88,38 @@ def torch_episode_window_push(rows, count, info, terminated, truncated, skip=Non
     rows.copy_(ring[:window])
     count += total
     return rows, count
+
+
+def torch_episode_window_push_log(rows, count, lost, log_rows, log_step, log_count):
+    """``salp_episode_window_push_log`` (include/salp.h) as torch ops without a
+    host sync, in place on ``rows`` [window, 20] f64, ``count`` and ``lost``
+    [1] int64.  The log: ``log_rows`` [n, K, 20] f64, ``log_step`` [n, K] and
+    ``log_count`` [n] int32.  The kept episodes are sorted by (step, env) from
+    the top; the g-th from the top is episode ``count + D - 1 - g``."""
+    window, (n, K) = rows.shape[0], log_step.shape
+    dev = rows.device
+    cnt = log_count.to(torch.int64).clamp(min=0).unsqueeze(1)             # [n, 1]
+    slot = torch.arange(K, device=dev).unsqueeze(0)                        # [1, K]
+    kept = slot < cnt
+    # a wrapped ring's slot holds the env's latest episode e with e % K == slot
+    e = (cnt - 1) // K * K + slot
+    e = torch.where(e > cnt - 1, e - K, e)
+    oldest_of_dropper = kept & (cnt > K) & (e == cnt - K)
+    env = torch.arange(n, device=dev).unsqueeze(1)
+    key = torch.where(kept, log_step.to(torch.int64) * n + env, torch.full_like(e, -1)).reshape(-1)
+    D, M = cnt.sum(), kept.sum()
+    S = min(window, n * K)
+    top = torch.argsort(key, descending=True)[:S]                          # distinct keys: the kept ones first
+    g = torch.arange(S, device=dev)
+    valid = g < M
+    row = torch.where(valid, (count + D - 1 - g) % window, torch.full_like(g, window))
+    # candidates that do not write go to one row past the ring, which is dropped
+    ring = torch.cat([rows, rows.new_zeros(1, rows.shape[1])])
+    ring[row] = log_rows.reshape(n * K, -1)[top]
+    rows.copy_(ring[:window])
+    lost += (valid & oldest_of_dropper.reshape(-1)[top]).sum()
+    count += D
+    return rows, count, lost
 
 
 def torch_episode_window_summary(rows, count):
@@ -166,6 +199,7 @@ class EpisodeWindow:
         self.fused = _fused(fused, self.device, "EpisodeWindow")
         self.rows = torch.full((self.window, _lib.EPWIN_COLS), math.nan, dtype=torch.float64, device=self.device)
         self.count = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self.lost = torch.zeros(1, dtype=torch.int64, device=self.device)   # push_log: envs whose dropped episodes may be missing
         self._c = None
         if self.fused:
             self._c = _lib.SalpEpisodeWindow(self.window, 0, self.rows.data_ptr(), self.count.data_ptr())
@@ -185,6 +219,23 @@ class EpisodeWindow:
                                  skip.data_ptr() if skip is not None else None)
         _lib.check(_lib.load().salp_episode_window_push(ctypes.byref(self._c), ctypes.byref(p), _stream(self.device)))
 
+    def push_log(self, log, n_envs=None):
+        """One chained collection's :class:`EpisodeLog`: the window afterwards
+        is what a :meth:`push` after every env-step of the collection would
+        have left, unless an env finished more episodes than the log keeps and
+        one of the dropped ones might have belonged to the window; ``lost``
+        [1] int64 counts those envs (0: the window is exact).  One launch, no
+        host traffic."""
+        n = log.n_envs if n_envs is None else int(n_envs)
+        if n != log.n_envs or log.device != self.device:
+            raise ValueError(f"EpisodeWindow.push_log: the log holds {log.n_envs} envs on {log.device}")
+        if not self.fused:
+            torch_episode_window_push_log(self.rows, self.count, self.lost, log.rows, log.step, log.count)
+            return
+        _lib.check(_lib.load().salp_episode_window_push_log(ctypes.byref(self._c), ctypes.byref(log.c_struct()), n,
+                                                            ctypes.c_void_p(self.lost.data_ptr()),
+                                                            _stream(self.device)))
+
     def summary_tensor(self):
         """The [84] summary on the device (include/salp.h salp_episode_window_summary)."""
         if not self.fused:
@@ -197,6 +248,29 @@ class EpisodeWindow:
     def summary(self):
         """:func:`summary_dict` of the window (synchronises: one host copy)."""
         return summary_dict(self.summary_tensor().tolist())
+
+
+class EpisodeLog:
+    """The caller-owned log of ``salp_collect_episodes`` (include/salp.h):
+    ``rows`` [n_envs, per_env, 20] f64 (NaN until written), ``step`` [n_envs,
+    per_env] int32 (-1 until written) and ``count`` [n_envs] int32.  Env ``i``'s
+    ``e``-th episode of a collection is in slot ``e % per_env``;
+    :meth:`BatchedSalpEnv.collect(..., episode_log=log)
+    <grasp_lab_salp_amd.batched_env.BatchedSalpEnv.collect>` fills it and
+    :meth:`EpisodeWindow.push_log` merges it."""
+
+    def __init__(self, n_envs, per_env, device="cuda"):
+        self.n_envs, self.per_env = int(n_envs), int(per_env)
+        if self.n_envs < 1 or self.per_env < 1:
+            raise ValueError("n_envs and per_env must be positive")
+        self.device = _device(device)
+        self.rows = torch.full((self.n_envs, self.per_env, _lib.EPWIN_COLS), math.nan, dtype=torch.float64,
+                               device=self.device)
+        self.step = torch.full((self.n_envs, self.per_env), -1, dtype=torch.int32, device=self.device)
+        self.count = torch.zeros(self.n_envs, dtype=torch.int32, device=self.device)
+
+    def c_struct(self):
+        return _lib.SalpEpisodeLog(self.per_env, self.rows.data_ptr(), self.step.data_ptr(), self.count.data_ptr())
 
 
 class EvalAccount:

@@ -50,6 +50,7 @@ import torch.distributed as dist
 from torch import nn
 
 from . import _lib
+from .metrics import EpisodeLog
 from ._abi import INFO, OBS_DIM_MAX, POLICY_OFFSETS, POLICY_SIZE
 
 __all__ = ["compute_gae", "ppo_loss", "torch_ppo_loss", "ActorCritic", "SplitKLinear", "RolloutBuffer", "PPO",
@@ -370,6 +371,21 @@ def _mlp_tensors(pol):
             pol.value_net.weight, pol.value_net.bias]
 
 
+EPISODE_LOG_MAX_ROWS = 65536   # rows of an episode log (20 doubles each: 10.5 MB) before its rings get shorter
+
+
+def episode_log_per_env(n_envs, n_steps, window):
+    """Episodes an :class:`~grasp_lab_salp_amd.metrics.EpisodeLog` keeps per
+    env for callbacks with windows up to ``window``.  ``min(n_steps, window)``
+    can never lose an episode of the window: an env ends at most ``n_steps``
+    episodes per collection, and its last ``window`` cover every one of its
+    episodes among the collection's last ``window``.  Beyond 65 536 rows the
+    rings shrink to ``max(2, 65 536 // n_envs)`` and the merge reports what may
+    be missing (``EpisodeWindow.lost``)."""
+    k = min(int(n_steps), int(window))
+    return k if n_envs * k <= EPISODE_LOG_MAX_ROWS else max(2, EPISODE_LOG_MAX_ROWS // n_envs)
+
+
 def _check_fused_act(policy, device):
     """``fused_act=True`` needs a GPU and the policy salp_ppo_mlp_act is built for."""
     if torch.device(device).type != "cuda":
@@ -459,13 +475,21 @@ class PPO:
     3 % less at 1 024 and 6.5 % less at 32 768 (the policy is a small share of
     a lock-step env-step: 101 -> 73 launches at 4 envs), ``evaluate`` on 5 envs
     65 % less.  It is off unless asked for so that the default path stays the
-    one every earlier figure was measured on."""
+    one every earlier figure was measured on.
+
+    ``episode_log`` (default 0: off, nothing allocated; ``True``: 100; an
+    integer: the largest window a callback may use; ``collect="chained"`` on a
+    GPU only): the chained collection kernels record every finished episode's
+    metrics row in a per-env log (``salp_collect_episodes``), which
+    ``DetailedMetricsCallback`` merges into its window once per collection
+    (DESIGN.md §6e).  ``locals`` is then ``{"episode_log": log}`` during
+    ``on_steps``."""
 
     def __init__(self, policy, env, learning_rate=3e-4, n_steps=2048, batch_size=64, n_epochs=10, gamma=0.99,
                  gae_lambda=0.95, clip_range=0.2, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5,
                  normalize_advantage=True, seed=0, device=None, verbose=0, reset_nonfinite=True,
                  use_graphs=None, fused_loss=None, collect="auto", fused_update=None, max_graph_minibatches=1024,
-                 fused_act=False):
+                 fused_act=False, episode_log=0):
         if policy not in ("MlpPolicy", None) and not isinstance(policy, nn.Module):
             raise ValueError("policy must be 'MlpPolicy' or an nn.Module")
         if fused_loss and isinstance(policy, nn.Module) and not all(
@@ -559,6 +583,19 @@ class PPO:
             self._packed = torch.empty(POLICY_SIZE, dtype=torch.float32, device=self.device)
             self._last_obs = torch.empty((self.n_envs, self.obs_dim), dtype=torch.float32, device=self.device)
             self._noise_seed = int(seed) + 1_000_003 * (dist.get_rank() if multi else 0)
+        # the chained collection's in-kernel episode log (salp_collect_episodes): 0 off, True 100,
+        # an integer the largest window a callback may use
+        self.episode_log = 100 if episode_log is True else int(episode_log or 0)
+        self._episode_log = None
+        if self.episode_log:
+            if not 1 <= self.episode_log <= _lib.EPWIN_MAX_WINDOW:
+                raise ValueError(f"episode_log must be 0, True or a window in 1 .. {_lib.EPWIN_MAX_WINDOW}")
+            if collect != "chained" or self.device.type != "cuda":
+                raise ValueError('episode_log records episodes inside the chained collection kernels: it needs '
+                                 'collect="chained" on a GPU (the lock-step collection hands callbacks every '
+                                 "env-step's tensors as it is)")
+            self._episode_log = EpisodeLog(self.n_envs, episode_log_per_env(self.n_envs, self.n_steps,
+                                                                            self.episode_log), self.device)
         self.num_timesteps = 0
         self.logger = {}
         self.timing = {"collect_s": 0.0, "gae_s": 0.0, "train_s": 0.0}
@@ -763,12 +800,12 @@ class PPO:
                          self._episode_starts, self._last_obs, self._ep_stats, self._nonfinite.view(1),
                          noise_seed=self._noise_seed, gamma=self.gamma,
                          diverged_obs_abs=DIVERGED_OBS_ABS if guard else 0.0,
-                         diverged_reward_abs=DIVERGED_REWARD_ABS if guard else 0.0)
+                         diverged_reward_abs=DIVERGED_REWARD_ABS if guard else 0.0, episode_log=self._episode_log)
         self._obs = self._last_obs
         if self._on_collect is not None:
             # no env-step boundary on the host: callbacks run once per collection, here
             self.num_timesteps += self.n_steps * self.n_envs
-            self.locals = {}
+            self.locals = {} if self._episode_log is None else {"episode_log": self._episode_log}
             if not self._on_collect():
                 return None   # training ends after this collection: no GAE, no update
         with torch.no_grad():
@@ -947,8 +984,8 @@ class PPO:
         layout (``.zip`` is appended to a ``path`` without a suffix; stored,
         not deflated; SB3 cannot read it): ``data.json`` (format tag and
         version, hyperparameters, ``collect``, ``fused_update``,
-        ``fused_loss``, ``fused_act``, ``num_timesteps``, ``seed``,
-        ``obs_dim``, ``device_type``), ``policy.pth``,
+        ``fused_loss``, ``fused_act``, ``episode_log``, ``num_timesteps``,
+        ``seed``, ``obs_dim``, ``device_type``), ``policy.pth``,
         ``policy.optimizer.pth`` (torch Adam's ``state_dict`` layout over
         ``policy.parameters()`` whichever update path wrote it: the fused
         step's flat moments are cut into it, so a file loads into either path)
@@ -963,7 +1000,7 @@ class PPO:
         data = {"format": self.FORMAT, "version": self.FORMAT_VERSION, "hyperparameters": hp,
                 "collect": self.collect, "fused_update": bool(self.fused_update), "fused_loss": bool(self.fused_loss),
                 "fused_act": bool(self.fused_act), "num_timesteps": int(self.num_timesteps), "seed": self.seed,
-                "obs_dim": self.obs_dim, "device_type": self.device.type}
+                "obs_dim": self.obs_dim, "device_type": self.device.type, "episode_log": int(self.episode_log)}
         files = {"policy.pth": {k: cpu(v) for k, v in self.policy.state_dict().items()},
                  "policy.optimizer.pth": self._optimizer_state(),
                  "rng.pth": {"sample_gen": self.sample_gen.get_state().clone(), "gen": self.gen.get_state().clone()}}
@@ -1014,6 +1051,8 @@ class PPO:
         hp["collect"] = data["collect"] if gpu else "lockstep"
         hp["seed"] = data["seed"]
         hp.update(kwargs)
+        if "episode_log" not in kwargs:   # a file from before the key: off; kept where the collection is still chained
+            hp["episode_log"] = int(data.get("episode_log", 0)) if gpu and hp["collect"] == "chained" else 0
         m = cls(hp.pop("policy", "MlpPolicy"), env, device=device, **hp)
         if m.obs_dim != data["obs_dim"]:
             raise ValueError(f"{path}: saved with obs_dim {data['obs_dim']}, the env has {m.obs_dim}")

@@ -395,7 +395,11 @@ class RecurrentPPO(PPO):
     def __init__(self, policy, env, learning_rate=3e-4, n_steps=2048, batch_size=64, n_epochs=10, gamma=0.99,
                  gae_lambda=0.95, clip_range=0.2, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5,
                  normalize_advantage=True, seed=0, device=None, verbose=0, reset_nonfinite=True,
-                 policy_kwargs=None, seq_len=16, use_graphs=None, fused_step=False, tensorboard_log=None):
+                 policy_kwargs=None, seq_len=16, use_graphs=None, fused_step=False, tensorboard_log=None,
+                 episode_log=0):
+        if episode_log:
+            raise ValueError("RecurrentPPO collects in lock-step (callbacks see every env-step's tensors): "
+                             "episode_log must be 0")
         sim = getattr(env, "sim", env)
         if device == "auto":    # sb3's default: here the simulator's device
             device = None

@@ -216,6 +216,35 @@ typedef struct SalpPolicyRollout {
 } SalpPolicyRollout;
 int salp_collect(SalpEnv* h, const SalpPolicyRollout* r, void* stream);
 
+/* salp_collect that also records the episodes it finishes (added under ABI 14
+ * without a new number: a library without the feature lacks the symbol).  The
+ * caller owns a per-env log; salp_collect is this call with a NULL log, and a
+ * call with a log leaves every salp_collect output (buffers, state, ep_stats,
+ * diverged) as the call without one does.
+ *
+ * A row is written exactly where ep_stats is updated: for an episode that
+ * ended by the task's rules (terminated or truncated) in an env-step the
+ * divergence guard did not drop; an env the guard reset logs nothing (the
+ * lock-step callback's skip = diverged).  The row is the episode-window row
+ * (SalpEpisodeWindow below, SALP_EPWIN_COLS = 20 doubles): ep_return, ep_len,
+ * success = terminated, truncation = truncated and not terminated, then info
+ * columns SALP_INFO_PATH_LENGTH .. SALP_INFO_AVG_R_OBSTACLE of that env-step,
+ * bit for bit what salp_step's info_out holds for the same step.  Env i's e-th
+ * episode of the call (0-based) goes to slot e % per_env of its own ring, with
+ * step = the buffer row t it ended in; count[i] is the number of episodes env i
+ * finished in this call, however many are still kept.  count is zeroed and
+ * rewritten by every call; slots a call does not reach keep their contents.
+ * An env is owned by one lane at a time: no atomics, two runs give the same bits.
+ * SALP_EINVAL, with a message and no GPU work: per_env < 1, or a NULL rows /
+ * step / count in a non-NULL log (and everything salp_collect rejects). */
+typedef struct SalpEpisodeLog {
+    int64_t per_env;       /* K >= 1: episodes kept per env, its latest K of the call */
+    double* rows;          /* [n_envs][K][SALP_EPWIN_COLS] */
+    int32_t* step;         /* [n_envs][K] */
+    int32_t* count;        /* [n_envs] written by every call, not accumulated */
+} SalpEpisodeLog;
+int salp_collect_episodes(SalpEnv* h, const SalpPolicyRollout* r, const SalpEpisodeLog* log, void* stream);
+
 /* Launch order of the lock-step calls (salp_step, salp_step_random): a
  * launch lasts as long as its slowest wave.  mode 1: envs run sorted by the
  * predicted length of the cycle each is about to run (longest first): the
@@ -766,6 +795,23 @@ typedef struct SalpEpisodePush {
  * `window` of them are written, so no two finishers of a push write one row.
  * One workgroup; any n_envs >= 1. */
 int salp_episode_window_push(const SalpEpisodeWindow* w, const SalpEpisodePush* p, void* stream);
+/* Merge one salp_collect_episodes log into the window: afterwards rows and
+ * count equal what n_steps calls of salp_episode_window_push would have left,
+ * one per buffer row t = 0, 1, ... in turn, each pushing the envs whose episode
+ * ended in row t in ascending env index.  With D = sum of count[i] (dropped
+ * episodes included) and c = count[0] on entry, the episode of rank r in
+ * (t, i) order becomes episode c + r in row (c + r) % window; only the last
+ * min(window, D) are written; count[0] += D.
+ * An env with count[i] > per_env has dropped its older episodes.  If that
+ * env's oldest kept episode is among the last `window` kept episodes (by
+ * (t, i)), one of its dropped ones might have belonged to the window: lost[0]
+ * += 1 for that env.  lost unchanged guarantees the window is exact; either
+ * way the result depends on the log's contents alone.  One workgroup, any
+ * n_envs >= 1 and per_env >= 1, no floating-point atomics, rows copied as
+ * 64-bit integers.  SALP_EINVAL with no GPU work: window outside 1 ..
+ * SALP_EPWIN_MAX_WINDOW, n_envs < 1, per_env < 1, a NULL pointer. */
+int salp_episode_window_push_log(const SalpEpisodeWindow* w, const SalpEpisodeLog* log, int64_t n_envs,
+                                 int64_t* lost, void* stream);
 /* What src/tensorboard_callback.py:131-205 computes.  out [SALP_EPSUM_DIM]:
  *   out[0] = n = min(count, window)
  *   out[1 + 4 c + {0, 1, 2, 3}] = mean, population standard deviation (two-pass,

@@ -211,6 +211,9 @@ def main():
     ap.add_argument("--collect-only", type=int, default=0, metavar="K", help="one collection of K env-steps, no update")
     ap.add_argument("--fused-act", action="store_true", help="PPO(fused_act=True) (with --collect-only)")
     ap.add_argument("--ab-fused-act", metavar="OUT.json", help="lock-step PPO, fused_act off / on in turn in one process")
+    ap.add_argument("--episode-log", action="store_true",
+                    help="PPO(episode_log=True) with DetailedMetricsCallback(log_freq=n_steps): the chained collection "
+                         "records its episodes in the kernel; also times the merge kernel alone")
     a = ap.parse_args()
     if a.reference_config:
         a.n_envs, a.n_steps, a.batch_size, a.seq_len, a.recurrent = 4, 2048, 64, 16, True
@@ -236,11 +239,15 @@ def main():
                              fused_step=a.fused_step)
     else:
         model = PPO("MlpPolicy", env, n_steps=a.n_steps, batch_size=a.batch_size, n_epochs=a.n_epochs, seed=0,
-                    collect=a.collect, use_graphs=False if a.no_graphs else None)
+                    collect=a.collect, use_graphs=False if a.no_graphs else None, episode_log=a.episode_log)
+    callback = None
+    if a.episode_log:
+        from grasp_lab_salp_amd.callbacks import DetailedMetricsCallback
+        callback = DetailedMetricsCallback(log_freq=a.n_steps)
     # warm-up (+ trend) iterations, one learn() call each so that a long trend
     # reports progress on stderr (a GPU job silent for minutes looks hung)
     for it in range(max(1, a.trend_iters)):
-        model.learn((it + 1) * a.n_steps * a.n_envs)
+        model.learn((it + 1) * a.n_steps * a.n_envs, callback=callback)
         if rank == 0:
             print(json.dumps(model.history[-1]), file=sys.stderr, flush=True)
     trend = list(model.history)
@@ -252,9 +259,23 @@ def main():
     t0 = time.perf_counter()
     model.num_timesteps = 0
     h0 = len(model.history)
-    model.learn(a.iters * a.n_steps * a.n_envs)
+    model.learn(a.iters * a.n_steps * a.n_envs, callback=callback)
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
+    merge = None
+    if a.episode_log:   # the merge kernel alone, on the last collection's log (into a scratch window)
+        from grasp_lab_salp_amd.metrics import EpisodeWindow
+        log, win = model._episode_log, EpisodeWindow(callback.window_size, model.device)
+        win.push_log(log)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(20):
+            win.push_log(log)
+        e1.record()
+        torch.cuda.synchronize()
+        merge = {"ms": e0.elapsed_time(e1) / 20, "per_env": log.per_env, "episodes_in_log": int(log.count.sum()),
+                 "window_count": int(callback.window.count), "lost": int(callback.window.lost),
+                 "log_bytes": sum(t.numel() * t.element_size() for t in (log.rows, log.step, log.count))}
     el, steps, _, _ = reduce_run(el, model.num_timesteps, 0.0, 0.0, device=torch.device("cuda", local))
     if rank == 0:
         res = {"metric": "PPO env-steps/sec (collect + GAE + update), config 5", "value": steps / el,
@@ -262,7 +283,8 @@ def main():
                "batch_size": a.batch_size, "n_epochs": a.n_epochs, "iters": a.iters, "collect": model.collect,
                "policy": (f"MlpLstmPolicy (LSTM {a.lstm_hidden}, seq_len {a.seq_len})" if a.recurrent
                           else "MlpPolicy 64-64 tanh"),
-               "timing_s": model.timing, "losses": model.logger,
+               "timing_s": model.timing, "episode_log": model.episode_log, "merge_kernel": merge,
+               "losses": model.logger,
                "history": model.history[h0:], "trend": trend if a.trend_iters else None,
                "diverged_envs_reset": model.nonfinite_resets,
                "gae_kernel": gae_roofline(a.gae_steps, a.n_envs)}
